@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the pre-train hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Under a launcher (``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``:
 RANK / LOCAL_RANK / WORLD_SIZE in the environment) this process IS a rank; without one, ``python bench.py --gpus N`` starts that
@@ -13,7 +13,14 @@ A "step" = one pass of the hot path over one synthetic batch, exactly the refere
 backward -> (flat RCCL gradient all-reduce when N>1) -> RAdam step.  bf16 storage, fp32 accumulation/statistics/loss
 (BASELINE.json configs[1]).  Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds of one timed step, and the configuration).  ``--dump-outputs DIR`` then also writes what the
+last timed step computed (the loss it returns, the updated flat parameters, the flat gradient the update consumed, the
+BatchNorm running statistics) as DIR/<name>.npy in float32; the inputs are seeded, so two builds compare output for output.
+
+``--full`` also measures everything the headline does not need, after the timed region (each still switched off by its
+--no-* flag): the per-replay distribution and the extra workloads (--no-extras), the live roofline (--no-roofline, a
+rocprofv3 child), the CPU oracle (--no-cpu-baseline) and, with N > 1, the collective alone.  Extra objects in the line:
   roofline      the dominant kernel of the step -- one __global__ template with ALL its instantiations' launches together
                 (conv3x3_fast_kernel: 17 launches, 42 % of the step) --, timed live with HIP events on its own stream in an
                 instrumented pass right after the timed region; algorithmic bytes/FLOPs as defined in DESIGN.md
@@ -107,7 +114,20 @@ def parse():
     ap.add_argument("--workload", default="pretrain", choices=["pretrain", "contrastive", "finetune", "prostate"],
                     help="pretrain = BASELINE configs[1] (the metric); prostate = configs[3] shape: 256x256, bs=64/GPU, "
                          "three self-paced hooks (partition, patient, self) sharing one encoder pass")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need, after the timed region: per-replay distribution and "
+                         "extra workloads, live roofline, CPU baseline, the collective alone (N > 1); the --no-* flags "
+                         "still switch single parts off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload == "contrastive":
+        ap.error("--dump-outputs: the training-step workloads (pretrain, prostate, finetune)")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_extras = args.no_roofline = args.no_cpu_baseline = True
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ step construction
@@ -569,6 +589,35 @@ def cpu_baseline(args):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(step, loss):
+    """what one training step hands its caller: the loss it returns, and the state it leaves -- the updated flat parameters,
+    the flat gradient its update consumed (the ranks' mean), the model's BatchNorm running statistics"""
+    flat = step.flat
+    buffers = [b.detach().reshape(-1).float() for n, b in step.model.named_buffers()
+               if b.is_floating_point() and ("running_mean" in n or "running_var" in n)]
+    return {"loss": loss.detach().reshape(-1), "params": flat.param.detach(), "grads": flat.flat * flat.grad_scale,
+            "bn_running": torch.cat(buffers) if buffers else torch.zeros(0)}
+
+
+def dump_outputs(dirname, arrays):
+    """every array as ``dirname/<name>.npy`` in float32 (float64 stays float64)"""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        out[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ main
 def spawn_ranks(args):
     """``python bench.py --gpus N`` (N > 1) without a launcher: start ``python -m torch.distributed.run --nnodes=1
@@ -706,7 +755,7 @@ def main():
     host = []
     for _ in range(args.steps):
         h0 = time.perf_counter()
-        run()
+        loss = run()
         host.append(time.perf_counter() - h0)
     torch.cuda.synchronize()
     if os.environ.get("SPCL_BENCH_HOSTDIAG") == "1" and rank == 0:
@@ -716,6 +765,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # (before anything below runs another step)
+        wd.beat("dump outputs")
+        dump_outputs(args.dump_outputs, step_outputs(step, loss))
     wd.beat("reduce")
     multi = None
     if world > 1:
@@ -726,6 +778,8 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+        multi = {"per_rank_ms_per_step": [round(float(v), 4) for v in per_rank.tolist()]}
+    if world > 1 and args.full:
         # ... and the step's one collective alone: HIP events around the epocher's exchange (flat bucket, communication
         # stream, both stream waits included), median of 20 after 5 warm calls, MAX over the ranks
         xs = []
@@ -740,10 +794,9 @@ def main():
         xs.sort()
         ar = torch.tensor([xs[len(xs) // 2]], device=device, dtype=torch.float64)
         dist.all_reduce(ar, op=dist.ReduceOp.MAX)
-        multi = {"per_rank_ms_per_step": [round(float(v), 4) for v in per_rank.tolist()],
-                 "allreduce_us": round(float(ar.item()), 1),
-                 "allreduce_note": "the flat gradient bucket's all-reduce alone on an idle GPU, HIP events on the caller's stream "
-                                   "(median of 20, max over ranks)"}
+        multi.update({"allreduce_us": round(float(ar.item()), 1),
+                      "allreduce_note": "the flat gradient bucket's all-reduce alone on an idle GPU, HIP events on the "
+                                        "caller's stream (median of 20, max over ranks)"})
     # per-replay distribution AFTER the timed region (HIP events on the launch stream around every single replay):
     # median / p10 / p90 of one step's GPU time -- an extra key, `value` stays the wall-clock aggregate above
     replay = None
@@ -1034,6 +1087,7 @@ def build_finetune_step(args, device):
         with ep.meters.focus_on(ep.meter_focus):
             return ep.step(next(loader))
 
+    step.flat, step.model = flat, model
     return step, ep
 
 
@@ -1049,9 +1103,11 @@ def bench_finetune(args, device):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        loss = run()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(step, loss))
     stats = ep.meters.statistics()["semi"]
     line = {"metric": "fine-tune slices/sec (full UNet + KL_div, 224^2)", "value": round(args.bs / dt, 1),
             "unit": "slices/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,

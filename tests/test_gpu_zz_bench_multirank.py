@@ -70,7 +70,7 @@ def _run_two_ranks(tmp_path, cmd, n=2, graphs="epocher-split"):
     return line
 
 
-BENCH_ARGS = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--bs", "4", "--size", "64", "--no-extras"]
+BENCH_ARGS = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--bs", "4", "--size", "64", "--no-extras", "--full"]
 
 
 def test_bench_two_ranks_on_one_device(tmp_path):

@@ -8,5 +8,5 @@ trap 'env -u SPCL_BUILD_DEFS -u SPCL_BUILD_ARCH -u SPCL_BUILD_NOSLP python self-
 for i in $(seq $R); do for v in "$A" "$B"; do
   SPCL_BUILD_DEFS="$v" python self-paced-contrastive-learning_amd/build.py --force > /dev/null 2>&1
   echo -n "defs='$v' "
-  python bench.py --no-cpu-baseline --no-roofline --steps 100 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], 'median', d['replay_us']['median'], 'p10', d['replay_us']['p10'])"
+  python bench.py --full --no-cpu-baseline --no-roofline --steps 100 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], 'median', d['replay_us']['median'], 'p10', d['replay_us']['p10'])"
 done; done

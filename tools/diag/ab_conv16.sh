@@ -7,6 +7,6 @@
 for i in 1 2; do
   for cfg in "SPCL_CONV16_FUSED=0" "SPCL_CONV16_NW=1" "SPCL_CONV16_NW=2" "SPCL_CONV16_NW=4"; do
     echo -n "$cfg "
-    env $cfg python bench.py --no-cpu-baseline --no-roofline --steps 100 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], 'median', d['replay_us']['median'], 'p10', d['replay_us']['p10'])"
+    env $cfg python bench.py --full --no-cpu-baseline --no-roofline --steps 100 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], 'median', d['replay_us']['median'], 'p10', d['replay_us']['p10'])"
   done
 done

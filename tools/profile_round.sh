@@ -1,6 +1,6 @@
 #!/bin/bash
 # The round's profile records, in one GPU-box call:  bash tools/profile_round.sh r03   ->  gpurun_out/<tag>_*
-#   <tag>_bench.json                      python bench.py (the driver's command line)
+#   <tag>_bench.json                      python bench.py --full (the headline and every extra measurement)
 #   <tag>_kernel_stats_bench_graph.csv    rocprofv3 --kernel-trace --stats of the same command (per symbol and grid)
 #   <tag>_step_timeline.txt               per-launch timeline of one replayed step
 #   <tag>_pmc_hbm_traffic.json            HBM bytes per launch: two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE), eager steps
@@ -9,7 +9,7 @@ TAG=${1:-rXX}
 OUT=gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 rm -rf $OUT/prof_kt $OUT/prof_f $OUT/prof_w
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_kt -- python bench.py --no-cpu-baseline --no-extras --no-roofline --steps 40 > $OUT/${TAG}_kt_bench.json 2> $OUT/${TAG}_kt.err
 python tools/prof_summary.py $OUT/prof_kt $OUT/${TAG}_kernel_stats_bench_graph.csv 60 > $OUT/${TAG}_kernel_stats_bench_graph.txt 2>&1

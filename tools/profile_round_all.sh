@@ -8,7 +8,7 @@ OUT=gpurun_out
 export TMPDIR=/tmp
 bash tools/profile_round.sh $TAG
 for wl in contrastive finetune prostate; do
-  timeout 600 python bench.py --workload $wl > $OUT/${TAG}_bench_$wl.json 2> $OUT/${TAG}_bench_$wl.err
+  timeout 600 python bench.py --full --workload $wl > $OUT/${TAG}_bench_$wl.json 2> $OUT/${TAG}_bench_$wl.err
 done
 for wl in finetune prostate; do
   rm -rf $OUT/prof_tl
