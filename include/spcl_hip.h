@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 9
+#define SPCL_ABI_VERSION 10
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -793,6 +793,34 @@ int spcl_bnrelu_backward_fill_acc(const void* y, void* dact, int dact_stride, co
 int spcl_bnrelu_backward_rows_acc(const void* y, const void* dact, const void* dpool, const float* rows, int nrows, int dtype,
                                   int N, int H, int W, int C, int CS, const float* st4, int training, long long* acc,
                                   float* dgamma, float* dbeta, void* dy, void* stream);
+
+/* IIC criteria of the UDA-IIC baseline (csrc/iic.hip; semi_seg/hooks/discretemi.py, contrastyou/losses/iic_loss.py).
+ * lx / ly: cluster-head logits as pixel rows [N][H][W][ld] f32, subhead s in columns s*K .. s*K+K-1 (2 <= K <= 32); the grouped
+ * softmax is applied as the rows are read.  flags_x: uint8 [N] (bit 0 flips H, bit 1 flips W) applied to X by indexing, or NULL.
+ *   spcl_iic_joint_forward: J[s][dy][dx][i][j] = sum_{n,u,v} PX[n,s,i,u+dy-p,v+dx-p] PY[n,s,j,u,v] (PX = 0 outside the image),
+ *                    0 <= p <= 7, as 32.32 fixed-point words in jacc (spcl_iic_joint_workspace_bytes; zeroed by the call):
+ *                    bitwise deterministic.
+ *   spcl_iic_loss:   one launch for all subheads; reads the joint from jacc or from an f32 jf32 [S][T][T][K][K] (exactly one).
+ *                    dense = 1: IIDSegmentationLoss (global min-shift of each subhead, per-displacement normalisation,
+ *                    symmetrisation, marginals, eps 1e-16, / T^2); dense = 0: IIDLoss (T = 1, eps 1e-10).  loss = scale *
+ *                    sum over subheads; dj = d loss / d J; j_out (optional, with jacc) = J in f32; nan_flag (optional) =
+ *                    1 when the dense loss is NaN, else 0.  ws: spcl_iic_loss_workspace_bytes(S, T).
+ *   spcl_iic_joint_backward: d(logits) of X (at its flipped rows) and Y from dj (times *gscale when non-NULL); the
+ *                    columns s*K + k of dlx / dly are written, the others are left alone.
+ *   spcl_consistency_softmax_mse: weight * mean((softmax(flip(a)) - softmax(b))^2) over [N][H][W][C] f32 class maps (C <= 16),
+ *                    db = its gradient w.r.t. b for a unit upstream gradient (a gets none); ws:
+ *                    spcl_consistency_workspace_bytes(N, H, W).  The loss is a fixed-order sum: deterministic. */
+size_t spcl_iic_joint_workspace_bytes(int S, int K, int pad);
+int spcl_iic_joint_forward(const float* lx, const float* ly, long ld, int N, int H, int W, int S, int K, int pad,
+                           const uint8_t* flags_x, long long* jacc, void* stream);
+size_t spcl_iic_loss_workspace_bytes(int S, int T);
+int spcl_iic_loss(const long long* jacc, const float* jf32, int S, int K, int T, int dense, float scale, float* j_out,
+                  float* loss, float* dj, int* nan_flag, void* ws, size_t ws_bytes, void* stream);
+int spcl_iic_joint_backward(const float* lx, const float* ly, long ld, int N, int H, int W, int S, int K, int pad,
+                            const uint8_t* flags_x, const float* dj, const float* gscale, float* dlx, float* dly, void* stream);
+size_t spcl_consistency_workspace_bytes(int N, int H, int W);
+int spcl_consistency_softmax_mse(const float* a, const float* b, int N, int C, int H, int W, const uint8_t* flags_a,
+                                 float weight, float* loss, float* db, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,7 @@ _MIRRORED = {
     "contrastyou": "contrastyou",
     "contrastyou.losses": "contrastyou.losses",
     "contrastyou.losses.contrast_loss3": "contrastyou.losses.contrast_loss3",
+    "contrastyou.losses.iic_loss": "contrastyou.losses.iic_loss",
     "contrastyou.meters": "contrastyou.meters",
     "contrastyou.projectors": "contrastyou.projectors",
     "contrastyou.projectors.heads": "contrastyou.projectors.heads",
@@ -32,6 +33,8 @@ _MIRRORED = {
     "semi_seg.hooks.creator": "semi_seg.hooks.creator",
     "semi_seg.hooks.infonce": "semi_seg.hooks.infonce",
     "semi_seg.hooks.utils": "semi_seg.hooks.utils",
+    "semi_seg.hooks.discretemi": "semi_seg.hooks.discretemi",
+    "semi_seg.hooks.consistency": "semi_seg.hooks.consistency",
     "semi_seg.epochers": "semi_seg.epochers",
     "semi_seg.epochers.new_pretrain": "semi_seg.epochers.pretrain",
     "semi_seg.epochers.new_epocher": "semi_seg.epochers.finetune",

@@ -6,9 +6,12 @@ indices so checkpoints interchange (``_header.2.*`` / ``_header.4.*``; ``_projec
 from torch import nn
 
 from ... import functional as F_hip
-from .nn import _ProjectorHeadBase, Flatten, Normalize, Identical
+import torch
 
-__all__ = ["ProjectionHead", "DenseProjectionHead", "get_contrastive_projector", "get_contrastive_dense_projector"]
+from .nn import _ProjectorHeadBase, Flatten, Normalize, Identical, SoftmaxWithT
+
+__all__ = ["ProjectionHead", "DenseProjectionHead", "ClusterHead", "DenseClusterHead", "get_contrastive_projector",
+           "get_contrastive_dense_projector"]
 
 
 def get_contrastive_projector(*, head_type: str, pool_module, input_dim, hidden_dim, output_dim, normalize: bool):
@@ -83,3 +86,77 @@ class DenseProjectionHead(_ProjectorHeadBase):
         if self._normalize:
             return F_hip.l2norm_channels(out)
         return out
+
+
+# ---------------------------------------------------------------------------------------------- IIC cluster heads
+def init_sub_header(*, head_type, input_dim, num_clusters, normalize, T):
+    """heads.py:42-58 (same modules, same construction order: same initial weights under one seed)"""
+    if head_type == "linear":
+        return nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), Flatten(), nn.Linear(input_dim, num_clusters),
+                             Normalize() if normalize else Identical(), SoftmaxWithT(1, T=T))
+    return nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), Flatten(), nn.Linear(input_dim, 128), nn.LeakyReLU(0.01, inplace=True),
+                         nn.Linear(128, num_clusters), Normalize() if normalize else Identical(), SoftmaxWithT(1, T=T))
+
+
+def init_dense_sub_header(head_type, input_dim, hidden_dim, num_clusters, normalize, T):
+    """heads.py:61-75"""
+    if head_type == "linear":
+        return nn.Sequential(nn.Conv2d(input_dim, num_clusters, 1, 1, 0), Normalize() if normalize else Identical(),
+                             SoftmaxWithT(1, T=T))
+    return nn.Sequential(nn.Conv2d(input_dim, hidden_dim, 1, 1, 0), nn.LeakyReLU(0.01, inplace=True),
+                         nn.Conv2d(hidden_dim, num_clusters, 1, 1, 0), Normalize() if normalize else Identical(),
+                         SoftmaxWithT(1, T=T))
+
+
+class _ClusterHeadBase(_ProjectorHeadBase):
+    def _check_fast(self):
+        if self._head_type != "linear" or self._normalize or self._T != 1:
+            raise NotImplementedError(f"{type(self).__name__}: head_type={self._head_type!r}, normalize={self._normalize} "
+                                      "(the UDA-IIC hooks build linear heads without normalisation)")
+
+    def forward(self, features):
+        """list of S probability maps, as the reference returns them"""
+        lg = self.logits(features)
+        K = lg.shape[1] // len(self._headers)
+        return [(lg[:, s * K:(s + 1) * K] / self._T).softmax(1) for s in range(len(self._headers))]
+
+
+class ClusterHead(_ClusterHeadBase):
+    """heads.py:124-145: S subheads of global average pool -> Linear(C, K) -> softmax; parameters at ``_headers.{s}.2.*``"""
+
+    def __init__(self, *, input_dim: int, num_clusters=5, num_subheads=10, head_type="linear", T=1, normalize=False):
+        super().__init__(input_dim=input_dim, output_dim=num_clusters, head_type=head_type, normalize=normalize,
+                         pool_name="none", spatial_size=(1, 1))
+        self._num_clusters, self._num_subheads, self._T = num_clusters, num_subheads, T
+        self._headers = nn.ModuleList([
+            init_sub_header(head_type=head_type, input_dim=self._input_dim, num_clusters=self._num_clusters,
+                            normalize=self._normalize, T=self._T) for _ in range(self._num_subheads)])
+
+    def logits(self, features):
+        """[N, S*K, 1, 1] f32 logits of every subhead (pool + one product over the stacked weights: csrc/projector.hip)"""
+        self._check_fast()
+        w = torch.cat([h[2].weight for h in self._headers], 0)
+        b = torch.cat([h[2].bias for h in self._headers], 0)
+        out = F_hip.projector(features, w, b, None, None, False)
+        return out.view(out.shape[0], out.shape[1], 1, 1)
+
+
+class DenseClusterHead(_ClusterHeadBase):
+    """heads.py:149-169: S subheads of a 1x1 conv (C -> K) -> softmax over channels; parameters at ``_headers.{s}.0.*``"""
+
+    def __init__(self, *, input_dim: int, num_clusters=10, hidden_dim=64, num_subheads=10, T=1, head_type: str = "linear",
+                 normalize: bool = False):
+        super().__init__(input_dim=input_dim, output_dim=num_clusters, head_type=head_type, normalize=normalize,
+                         pool_name="none", spatial_size=(1, 1))
+        self._T = T
+        self._headers = nn.ModuleList([
+            init_dense_sub_header(head_type=head_type, input_dim=self._input_dim, hidden_dim=hidden_dim,
+                                  num_clusters=num_clusters, normalize=self._normalize, T=self._T)
+            for _ in range(num_subheads)])
+
+    def logits(self, features):
+        """[N, S*K, H, W] f32 logits (channels-last) of every subhead: one pixel-row product over the stacked weights"""
+        self._check_fast()
+        w = torch.cat([h[0].weight for h in self._headers], 0)
+        b = torch.cat([h[0].bias for h in self._headers], 0)
+        return F_hip.pixelwise_mlp(features, w, b)

@@ -61,3 +61,14 @@ class _ProjectorHeadBase(nn.Module):
         self._head_type, self._normalize = head_type, normalize
         self._pool_name, self._spatial_size = pool_name, _pair(spatial_size)
         self._pooling_module = get_pool_component(self._pool_name, self._spatial_size)
+
+
+class SoftmaxWithT(nn.Softmax):
+    """softmax of ``input / T`` along ``dim`` (nn.py:18-26)"""
+
+    def __init__(self, dim, T: float = 1.0) -> None:
+        super().__init__(dim)
+        self._T = T
+
+    def forward(self, input):
+        return super().forward(input / self._T)

@@ -2514,3 +2514,115 @@ def concat_channels(a, b, dtype):
     if a.shape[1] % 16 or b.shape[1] % 16:
         return torch.cat((a, b), dim=1)
     return _Concat2Fn.apply(a, b, dtype)
+
+
+# --------------------------------------------------------------------------------------------- IIC / consistency (csrc/iic.hip)
+IIC_DENSE, IIC_GLOBAL = 1, 0
+
+
+def _flip_flags_arg(flags, N, dev):
+    """per-sample flip flags as the kernels read them: a uint8 [N] tensor on the logits' device (the kernels index it
+    by sample), or None"""
+    if flags is None:
+        return None
+    _n.require_gpu(flags)
+    if flags.device != dev or flags.dtype != torch.uint8 or flags.dim() != 1 or flags.numel() != N:
+        raise ValueError(f"flip flags must be a uint8 [{N}] tensor on {dev}: got {flags.dtype} {tuple(flags.shape)} on "
+                         f"{flags.device}")
+    return flags.detach().contiguous()
+
+
+class _IICLossFn(torch.autograd.Function):
+    """The IIC criterion of S subheads in three launches: the joint of the grouped softmaxes of two logit maps (X read through
+    its per-sample flips), the loss with dJ (one launch for all subheads), and -- in backward -- d(logits) of both maps.
+    ``lx`` / ``ly``: logical [N, S*K, H, W] f32 logits (channels-last storage, as ``pixelwise_mlp`` returns them).
+    Returns the loss; ``out`` receives (J f32 [S,T,T,K,K], nan flag int32 [1])."""
+
+    @staticmethod
+    def forward(ctx, lx, ly, flags, S, K, pad, dense, scale, out):
+        _n.require_gpu(lx, ly)
+        xs, ys = _class_map_storage(lx.detach()), _class_map_storage(ly.detach())
+        if xs.shape != ys.shape or xs.shape[3] != S * K:
+            raise AssertionError(f"logit maps {tuple(xs.shape)} / {tuple(ys.shape)} do not hold {S} x {K} clusters")
+        N, H, W, ld = xs.shape
+        T, dev = 2 * pad + 1, xs.device
+        fl = _flip_flags_arg(flags, N, dev)
+        jacc = torch.empty(_n.call("spcl_iic_joint_workspace_bytes", S, K, pad) // 8, dtype=torch.int64, device=dev)
+        _n.call("spcl_iic_joint_forward", _n.ptr(xs), _n.ptr(ys), ld, N, H, W, S, K, pad, _n.ptr(fl), _n.ptr(jacc), _n.stream())
+        jf = torch.empty(S, T, T, K, K, dtype=torch.float32, device=dev)
+        dj = torch.empty_like(jf)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        flag = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(_n.call("spcl_iic_loss_workspace_bytes", S, T), dtype=torch.uint8, device=dev)
+        _n.call("spcl_iic_loss", _n.ptr(jacc), None, S, K, T, int(dense), c_float(scale), _n.ptr(jf), _n.ptr(loss), _n.ptr(dj),
+                _n.ptr(flag), _n.ptr(ws), ws.numel(), _n.stream())
+        out.extend([jf, flag])
+        ctx.save_for_backward(xs, ys, dj, fl)
+        ctx.meta = (S, K, pad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        xs, ys, dj, fl = ctx.saved_tensors
+        S, K, pad = ctx.meta
+        N, H, W, ld = xs.shape
+        gs = None if is_unit_gradient(g) else g.detach().float().reshape(1).contiguous()
+        dlx, dly = torch.empty_like(xs), torch.empty_like(ys)
+        _n.call("spcl_iic_joint_backward", _n.ptr(xs), _n.ptr(ys), ld, N, H, W, S, K, pad, _n.ptr(fl), _n.ptr(dj), _n.ptr(gs),
+                _n.ptr(dlx), _n.ptr(dly), _n.stream())
+        return dlx.permute(0, 3, 1, 2), dly.permute(0, 3, 1, 2), None, None, None, None, None, None, None
+
+
+def iic_loss(lx, ly, *, num_subheads, num_clusters, padding=0, dense=True, scale=1.0, flags=None, out=None):
+    """``scale * sum_s criterion(softmax(flip(lx)_s), softmax(ly_s))`` (IIDSegmentationLoss(padding) when ``dense``, IIDLoss
+    otherwise) of logical [N, S*K, H, W] logits; differentiable w.r.t. both maps.  ``out`` (a list) receives (J, nan flag)."""
+    return _IICLossFn.apply(lx, ly, flags, int(num_subheads), int(num_clusters), int(padding), bool(dense), float(scale),
+                            [] if out is None else out)
+
+
+def iic_loss_from_joint(j, *, dense=True, scale=1.0):
+    """-> (loss, dJ, nan flag) of an f32 joint [S, T, T, K, K] (spcl_iic_loss on a given J; a check tool for the criterion)"""
+    _n.require_gpu(j)
+    jc = j.detach().float().contiguous()
+    S, T, _, K, _ = jc.shape
+    loss = torch.empty((), dtype=torch.float32, device=jc.device)
+    dj = torch.empty_like(jc)
+    flag = torch.empty(1, dtype=torch.int32, device=jc.device)
+    ws = torch.empty(_n.call("spcl_iic_loss_workspace_bytes", S, T), dtype=torch.uint8, device=jc.device)
+    _n.call("spcl_iic_loss", None, _n.ptr(jc), S, K, T, int(dense), c_float(scale), None, _n.ptr(loss), _n.ptr(dj),
+            _n.ptr(flag), _n.ptr(ws), ws.numel(), _n.stream())
+    return loss, dj, flag
+
+
+class _ConsistencyFn(torch.autograd.Function):
+    """``weight * MSELoss(softmax(flip(a)).detach(), softmax(b))`` in one launch; the gradient w.r.t. ``b`` for a unit upstream
+    gradient is written by the same launch (``a`` gets none: the reference detaches it)."""
+
+    @staticmethod
+    def forward(ctx, a, b, flags, weight):
+        _n.require_gpu(a, b)
+        as_, bs = _class_map_storage(a.detach()), _class_map_storage(b.detach())
+        if as_.shape != bs.shape:
+            raise AssertionError(f"class maps {tuple(as_.shape)} / {tuple(bs.shape)} differ")
+        N, H, W, C = bs.shape
+        dev = bs.device
+        fl = _flip_flags_arg(flags, N, dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        db = torch.empty_like(bs)
+        ws = torch.empty(_n.call("spcl_consistency_workspace_bytes", N, H, W), dtype=torch.uint8, device=dev)
+        _n.call("spcl_consistency_softmax_mse", _n.ptr(as_), _n.ptr(bs), N, C, H, W, _n.ptr(fl), c_float(weight),
+                _n.ptr(loss), _n.ptr(db), _n.ptr(ws), ws.numel(), _n.stream())
+        ctx.save_for_backward(db)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (db,) = ctx.saved_tensors
+        if is_unit_gradient(g):
+            return None, db.permute(0, 3, 1, 2), None, None
+        return None, (db * g.detach().float()).permute(0, 3, 1, 2), None, None
+
+
+def consistency_softmax_mse(a, b, weight=1.0, flags=None):
+    """consistency.py:30-35: ``weight * mse(softmax(flip(a)).detach(), softmax(b))`` of logical [N, C, H, W] logits"""
+    return _ConsistencyFn.apply(a, b, flags, float(weight))

@@ -2,8 +2,9 @@
 
 Contract (hook_creator.py:10-28): ``InfonceParams`` builds plain InfoNCE hooks, ``SPInfonceParams`` the self-paced ones
 (they also get the trainer's ``max_epoch`` for their age-parameter schedule); both receive ``Data.name``.
-``DiscreteMIConsistencyParams`` is a comparison baseline outside the hot path: during pre-training the
-reference raises RuntimeError for it and so does this mirror; otherwise it is refused as not implemented."""
+``DiscreteMIConsistencyParams`` (the UDA-IIC baseline) builds the discrete-MI + consistency hooks
+(``create_discrete_mi_consistency_hook``) outside pre-training; during pre-training the reference raises RuntimeError for
+it and so does this mirror."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -26,5 +27,5 @@ def create_hook_from_config(model, config, is_pretrain=False):
     if _BASELINE_SECTION in config:
         if is_pretrain:
             raise RuntimeError(f"{_BASELINE_SECTION} are not supported for pretrain stage")
-        raise NotImplementedError(f"{_BASELINE_SECTION}: comparison baseline outside the HIP hot path")
+        built.append(_hooks.create_discrete_mi_consistency_hook(model=model, **config[_BASELINE_SECTION]))
     return built

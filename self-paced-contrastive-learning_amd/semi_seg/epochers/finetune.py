@@ -341,3 +341,7 @@ class FineTuneEpocher(_EpocherBase):
     def _run_only_label(self):
         for self.cur_batch_num, labeled_data in zip(range(self._num_batches), self._labeled_loader):
             self.step(labeled_data)
+
+
+# the reference's ``new_epocher`` module also holds the semi-supervised epocher
+from .semi import SemiSupervisedEpocher  # noqa: E402,F401

@@ -1,11 +1,14 @@
-"""Mirror of the InfoNCE factories in ``semi_seg/hooks/creator.py``: ``feature_until_from_hooks`` (:23-29),
+"""Mirror of the factories in ``semi_seg/hooks/creator.py``: ``feature_until_from_hooks`` (:23-29),
 ``create_infonce_hooks`` (:69-99) and ``create_sp_infonce_hooks`` (:102-124) -- one hook per (feature, weight,
-contrast_on) triple combined into one TrainerHook."""
+contrast_on) triple combined into one TrainerHook -- and the UDA-IIC factories ``create_consistency_hook`` (:32-33),
+``create_discrete_mi_hooks`` (:36-47) and ``create_discrete_mi_consistency_hook`` (:50-66)."""
 from typing import List, Union
 
 from ...contrastyou.hooks.base import CombineTrainerHook
 from ..arch.unet import sort_arch
-from .infonce import INFONCEHook, SelfPacedINFONCEHook
+from .consistency import ConsistencyTrainerHook
+from .discretemi import DiscreteMITrainHook
+from .infonce import INFONCEHook, SelfPacedINFONCEHook, decoder_names
 
 
 def _listify(v, n):
@@ -42,3 +45,53 @@ def create_sp_infonce_hooks(*, model, feature_names: Union[str, List[str]], weig
              for f, w, c, b, e, cg in zip(feature_names, _listify(weights, n), _listify(contrast_ons, n),
                                           _listify(begin_values, n), _listify(end_values, n), corr)]
     return CombineTrainerHook(*hooks)
+
+
+def ntuple(n):
+    """contrastyou/utils/utils.py:176-192: a scalar or a one-element list repeated n times; a list of another length
+    raises RuntimeError"""
+    from itertools import repeat
+
+    def parse(x):
+        if isinstance(x, str):
+            return tuple(repeat(x, n))
+        if isinstance(x, (list, tuple)):
+            x = list(x)
+            if len(x) == 1:
+                return tuple(repeat(x[0], n))
+            if len(x) != n:
+                raise RuntimeError(f"inconsistent shape between {x} and {n}")
+            return x
+        return tuple(repeat(x, n))
+
+    return parse
+
+
+def create_consistency_hook(weight: float):
+    return ConsistencyTrainerHook(name="consistency", weight=weight)
+
+
+def create_discrete_mi_hooks(*, feature_names: List[str], weights: List[float], paddings: List[int], model):
+    assert len(feature_names) == len(weights), (feature_names, weights)
+    decoder_features = [f for f in feature_names if f in decoder_names]
+    assert len(paddings) == len(decoder_features), (decoder_features, paddings)
+    _pad_gen = iter(paddings)
+    paddings_ = [next(_pad_gen) if f in decoder_features else None for f in feature_names]
+    hooks = [DiscreteMITrainHook(name=f"discreteMI/{f.lower()}", model=model, feature_name=f, weight=w, padding=p)
+             for f, w, p in zip(feature_names, weights, paddings_)]
+    return CombineTrainerHook(*hooks)
+
+
+def create_discrete_mi_consistency_hook(*, model, feature_names: Union[str, List[str]],
+                                        mi_weights: Union[float, List[float]], dense_paddings: List[int] = None,
+                                        consistency_weight: float):
+    n_features = 1 if isinstance(feature_names, str) else len(feature_names)
+    pair_generator = ntuple(n_features)
+    feature_names = pair_generator(feature_names)
+    mi_weights = pair_generator(mi_weights)
+    n_dense_features = len([f for f in feature_names if f in decoder_names])
+    dense_paddings = ntuple(n_dense_features)(dense_paddings)
+    discrete_mi_hook = create_discrete_mi_hooks(feature_names=feature_names, weights=mi_weights, paddings=dense_paddings,
+                                                model=model)
+    consistency_hook = create_consistency_hook(weight=consistency_weight)
+    return CombineTrainerHook(discrete_mi_hook, consistency_hook)

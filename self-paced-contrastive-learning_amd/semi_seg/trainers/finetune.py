@@ -136,3 +136,7 @@ class FineTuneTrainer:
         tmp = os.path.join(self._save_dir, name + ".tmp")
         torch.save(self.state_dict(), tmp)
         os.replace(tmp, os.path.join(self._save_dir, name))
+
+
+# the reference's ``new_trainer`` module also holds these (``main.py:15`` imports all three from it)
+from .semi import MixUpTrainer, SemiTrainer  # noqa: E402,F401

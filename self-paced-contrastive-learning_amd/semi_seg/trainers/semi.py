@@ -1,0 +1,77 @@
+"""Mirror of ``SemiTrainer`` (semi_seg/trainers/new_trainer.py:17-56): ``FineTuneTrainer``'s epoch loop, evaluation and
+best / last checkpoints with the hook registry of the pre-train trainer -- ``register_hooks`` before ``init()``, one flat
+parameter over model + hook parameters, ``__hooks__`` in the checkpoint -- and ``SemiSupervisedEpocher`` as the training
+epocher (``two_stage`` / ``disable_bn`` from the reference's keyword set).  ``MixUpTrainer`` is an import stub."""
+import torch
+from torch import nn
+
+from ... import ddp as _ddp
+from ..epochers.semi import SemiSupervisedEpocher
+from .finetune import FineTuneTrainer
+from .pretrain import WarmupCosine, build_optimizer
+
+
+class SemiTrainer(FineTuneTrainer):
+    activate_hooks = True
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.__hooks__ = nn.ModuleList()
+
+    # trainer/base.py:49-58
+    def register_hook(self, hook):
+        from ...contrastyou.hooks.base import TrainerHook
+        assert isinstance(hook, TrainerHook), hook
+        self.__hooks__.append(hook)
+
+    def register_hooks(self, *hooks):
+        if self.__initialized__:
+            raise RuntimeError("`register_hook must be called before `init()``")
+        for h in hooks:
+            self.register_hook(h)
+
+    def init(self):
+        self._model.to(self._device)
+        self.__hooks__.to(self._device)
+        _ddp.broadcast_state(self._model, self.__hooks__)
+        params = [p for p in self._model.parameters() if p.requires_grad]
+        hook_params = [p for h in self.__hooks__ for p in h.parameters()]
+        self._flat = _ddp.FlatParams(params + hook_params)
+        self._optimizer = build_optimizer(self._optim_name, self._flat.param, self._optim_cfg)
+        self._scheduler = None
+        if self._sched_cfg is not None:
+            self._scheduler = WarmupCosine(self._optimizer, max_epoch=self._max_epoch, **self._sched_cfg)
+        self.__initialized__ = True
+
+    @property
+    def train_epocher(self):
+        return SemiSupervisedEpocher
+
+    def _create_tra_epoch(self):
+        epocher = self.train_epocher(model=self._model, optimizer=self._optimizer, labeled_loader=self._labeled_loader,
+                                     unlabeled_loader=self._unlabeled_loader, sup_criterion=self._criterion,
+                                     num_batches=self._num_batches, cur_epoch=self._cur_epoch, device=self._device,
+                                     two_stage=self._two_stage, disable_bn=self._disable_bn, flat_params=self._flat)
+        if self.activate_hooks and len(self.__hooks__) > 0:
+            epocher.add_hooks([h() for h in self.__hooks__])
+        epocher.init()
+        return epocher
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["__hooks__"] = self.__hooks__.state_dict()
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        self.__hooks__.load_state_dict(sd["__hooks__"])
+
+    def resume_from_path(self, path):
+        self.load_state_dict(torch.load(path, map_location="cpu"))
+
+
+class MixUpTrainer(SemiTrainer):
+    """named by the reference's ``main.py:15`` import line; the mix-up baseline is not mirrored"""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("MixUpTrainer: the mix-up baseline is not mirrored")
