@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 10
+#define SPCL_ABI_VERSION 11
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -821,6 +821,32 @@ int spcl_iic_joint_backward(const float* lx, const float* ly, long ld, int N, in
 size_t spcl_consistency_workspace_bytes(int N, int H, int W);
 int spcl_consistency_softmax_mse(const float* a, const float* b, int N, int C, int H, int W, const uint8_t* flags_a,
                                  float weight, float* loss, float* db, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- mean teacher / entropy minimisation (csrc/semi_reg.hip) ----
+ * Replaces the arithmetic of semi_seg/hooks/mt.py:48-54 and semi_seg/hooks/entmin.py:30-34 of the reference.
+ *
+ *   spcl_ema_update: teacher[i] = (alpha * teacher[i] + (1 - alpha) * student[i]) * (1 - decay) over two flat f32 buffers of n
+ *                    elements in ONE launch (mt.py:54 -> deepclustering2 ema_updater: mul_(alpha), add_((1 - alpha) * s),
+ *                    mul_(1 - decay) per parameter tensor).  Three f32 roundings per element in that order; decay == 0 leaves
+ *                    the last multiplication out.  The buffers need 4-byte alignment only and must not overlap; alpha and decay
+ *                    are host values.
+ *   spcl_mt_softmax_mse: weight * mean((flip(T) - softmax(student_logits))^2) over [N][H][W][C] f32 class maps (C <= 16), the
+ *                    teacher map read through the per-sample flip flags (bit 0 flips H, bit 1 flips W); teacher_mode 0: T is the
+ *                    teacher's raw output (what mt.py:49-52 computes: its `prob` is never soft-maxed), 1: T = softmax(teacher)
+ *                    (_mixins.py:147).  dstudent = the gradient w.r.t. student_logits for a unit upstream gradient (the teacher
+ *                    gets none); ws: spcl_mt_softmax_mse_workspace_bytes(N, H, W).
+ *   spcl_entropy_softmax: weight * mean over the N*H*W pixels of -sum_c p_c log(p_c + eps), p = softmax(logits)
+ *                    (entmin.py:30-31 -> deepclustering2 Entropy); dlogits = its gradient for a unit upstream gradient; ws:
+ *                    spcl_entropy_softmax_workspace_bytes(N, H, W).
+ *   Both losses are fixed-order sums (per-workgroup double partials added in index order): bitwise reproducible. */
+int spcl_ema_update(float* teacher, const float* student, size_t n, double alpha, double decay, void* stream);
+size_t spcl_mt_softmax_mse_workspace_bytes(int N, int H, int W);
+int spcl_mt_softmax_mse(const float* teacher, const float* student_logits, int N, int C, int H, int W,
+                        const uint8_t* flags_teacher, int teacher_mode, float weight, float* loss, float* dstudent, void* ws,
+                        size_t ws_bytes, void* stream);
+size_t spcl_entropy_softmax_workspace_bytes(int N, int H, int W);
+int spcl_entropy_softmax(const float* logits, int N, int C, int H, int W, float eps, float weight, float* loss, float* dlogits,
+                         void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,8 @@ _MIRRORED = {
     "semi_seg.hooks.utils": "semi_seg.hooks.utils",
     "semi_seg.hooks.discretemi": "semi_seg.hooks.discretemi",
     "semi_seg.hooks.consistency": "semi_seg.hooks.consistency",
+    "semi_seg.hooks.mt": "semi_seg.hooks.mt",
+    "semi_seg.hooks.entmin": "semi_seg.hooks.entmin",
     "semi_seg.epochers": "semi_seg.epochers",
     "semi_seg.epochers.new_pretrain": "semi_seg.epochers.pretrain",
     "semi_seg.epochers.new_epocher": "semi_seg.epochers.finetune",
@@ -58,8 +60,8 @@ def install(strict: bool = False, reference_root: str = None):
 
     ``reference_root``: a checkout of the reference.  Its ``semi_seg`` / ``contrastyou`` directories are appended to the
     mirror packages' search paths, so every module that is NOT mirrored (data sets, configuration, writers) still comes
-    from the reference while the hot path comes from here.  ``deepclustering2.loss.KL_div`` (un-vendored third party) is
-    provided by the mirror's restatement only when that package cannot be imported."""
+    from the reference while the hot path comes from here.  ``deepclustering2.loss.KL_div`` and ``Entropy`` (un-vendored
+    third party) are provided by the mirror's restatement only when that package cannot be imported."""
     import importlib
     import os
     import sys
@@ -89,6 +91,7 @@ def install(strict: bool = False, reference_root: str = None):
         top = sys.modules.setdefault("deepclustering2", types.ModuleType("deepclustering2"))
         loss = types.ModuleType("deepclustering2.loss")
         loss.KL_div = _kl.KL_div
+        loss.Entropy = _kl.Entropy
         top.loss = loss
         sys.modules["deepclustering2.loss"] = loss
         done.append("deepclustering2.loss")

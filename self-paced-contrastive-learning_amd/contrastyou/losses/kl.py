@@ -38,3 +38,23 @@ class KL_div(nn.Module):
             assert simplex(prob), "prob is not a simplex"
             assert simplex(target), "target is not a simplex"
         return F_hip.kl_div(prob, target, self._eps)
+
+
+class Entropy(nn.Module):
+    """``deepclustering2.loss.Entropy(reduction='mean', eps=1e-16)(prob)`` = ``-(prob * (prob + eps).log()).sum(1).mean()``
+    as ``semi_seg/hooks/entmin.py:13,31`` calls it; asserts that the input is a simplex unless ``disable_assert=True``.
+    Restated from its published definition like ``KL_div`` above (deepclustering2 is not vendored).  This is the plain
+    float path on whatever device ``prob`` lives: the entropy hook does not materialise the softmax and call it, it runs
+    ``functional.entropy_softmax`` on the logits (one launch), which is checked against this class."""
+
+    def __init__(self, reduction="mean", eps=1e-16):
+        super().__init__()
+        if reduction != "mean":
+            raise NotImplementedError("Entropy mirror: reduction='mean' (what the reference uses)")
+        self._eps = eps
+
+    def forward(self, prob: torch.Tensor, **kwargs) -> torch.Tensor:
+        if not kwargs.get("disable_assert"):
+            assert prob.dim() >= 2, prob.shape
+            assert simplex(prob), "prob is not a simplex"
+        return -(prob * (prob + self._eps).log()).sum(1).mean()

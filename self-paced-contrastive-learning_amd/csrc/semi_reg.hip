@@ -1,0 +1,285 @@
+// Regularisers of the mean-teacher and entropy-minimisation baselines (semi_seg/hooks/mt.py, semi_seg/hooks/entmin.py).
+//
+//   spcl_ema_update:      the teacher's exponential moving average over ONE flat f32 buffer (mt.py:54 -> deepclustering2
+//                         ema_updater: mul_(alpha), add_((1 - alpha) * s), mul_(1 - decay) per parameter tensor, ~180 launches
+//                         for the UNet) as one launch.  12 bytes per element (read t, read s, write t), no reuse: bandwidth-
+//                         bound.  16-byte loads / stores over the part of the teacher that is 16-byte aligned, a scalar head
+//                         of up to 3 elements before it and a scalar tail of up to 3 behind it; the student is read with
+//                         16-byte loads when it shares the teacher's misalignment, with four 4-byte loads otherwise.  The grid
+//                         is capped at 2048 workgroups of 256 (8 per CU on 256 CUs), grid-stride beyond: the UNet's 2.16 M
+//                         parameters are 540 k granules over 524 k threads, 26 MB in all.  Measured 7.9 - 8.1 us per launch
+//                         (profiles/mt_step_time.txt; the buffers stay in the Infinity Cache between steps) against 0.77 ms
+//                         for the per-tensor torch formulation.
+//   spcl_mt_softmax_mse:  weight * mean((flip(T) - softmax(b))^2) and its gradient w.r.t. b in one launch; T = the teacher's
+//                         raw output (mt.py:49-52 applies no softmax) or its softmax (the older _mixins.py:147).
+//   spcl_entropy_softmax: weight * mean over pixels of -sum_c p_c log(p_c + eps), p = softmax(logits), and its gradient.
+//
+// Both criteria: one thread per pixel (C <= 16 channels in registers), per-workgroup double partials, the last workgroup
+// to take a ticket sums them in index order and resets the ticket: loss and gradient are bitwise reproducible.
+#include "common.hpp"
+
+namespace {
+
+__device__ __forceinline__ int flip_idx(int x, int n, bool f) { return f ? n - 1 - x : x; }
+
+// three f32 roundings, in the reference's order: t * alpha | + (1 - alpha) * s (one fused multiply-add, as torch's
+// add_(s, alpha=) computes it) | * (1 - decay).  DECAY = false leaves the last one out (no multiplication by 1.0).
+template <bool DECAY>
+__device__ __forceinline__ float ema_one(float t, float s, float alpha, float oma, float keep) {
+  const float r = fmaf(oma, s, t * alpha);
+  return DECAY ? r * keep : r;
+}
+
+// t + head is 16-byte aligned; n4 granules follow it; SVEC: s + head is 16-byte aligned too
+template <bool DECAY, bool SVEC>
+__global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ t, const float* __restrict__ s, size_t head,
+                                                         size_t n4, size_t n, float alpha, float oma, float keep) {
+  f32x4* tv = reinterpret_cast<f32x4*>(t + head);
+  const float* sb = s + head;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    f32x4 a = tv[i], b;
+    if (SVEC) {
+      b = reinterpret_cast<const f32x4*>(sb)[i];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) b[e] = sb[4 * i + e];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] = ema_one<DECAY>(a[e], b[e], alpha, oma, keep);
+    tv[i] = a;
+  }
+  if (blockIdx.x == 0) {  // scalar head (< 4 elements) and tail (< 4 elements): threads 0 .. 7
+    const size_t tail0 = head + 4 * n4;
+    const size_t k = threadIdx.x;
+    if (k < head) t[k] = ema_one<DECAY>(t[k], s[k], alpha, oma, keep);
+    else if (k >= 4 && tail0 + (k - 4) < n) {
+      const size_t i = tail0 + (k - 4);
+      t[i] = ema_one<DECAY>(t[i], s[i], alpha, oma, keep);
+    }
+  }
+}
+
+__device__ __forceinline__ double block_sum_d(double v, double* sh) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double r = 0.0;
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += sh[w];
+  return r;
+}
+
+// the workgroup's partial -> partial[blockIdx.x]; the last workgroup sums all of them in index order
+__device__ __forceinline__ void ordered_total(double v, double scale, float* __restrict__ loss, double* __restrict__ partial,
+                                              unsigned int* __restrict__ ticket) {
+  __shared__ unsigned int last;
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = v;
+    __threadfence();
+    last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (last && threadIdx.x == 0) {
+    __threadfence();
+    double tot = 0.0;
+    for (unsigned int q = 0; q < gridDim.x; ++q) tot += *((volatile double*)partial + q);
+    loss[0] = (float)(tot * scale);
+    *ticket = 0u;
+  }
+}
+
+// loss = weight * mean((flip(T) - softmax(b))^2); TSOFT: T = softmax(teacher), else T = teacher
+template <bool TSOFT>
+__global__ void __launch_bounds__(256) mt_mse_kernel(const float* __restrict__ a, const float* __restrict__ b, int N, int C,
+                                                     int H, int W, const uint8_t* __restrict__ flags, float weight,
+                                                     float* __restrict__ loss, float* __restrict__ db,
+                                                     double* __restrict__ partial, unsigned int* __restrict__ ticket) {
+  __shared__ double sh[8];
+  const long M = (long)N * H * W;
+  const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const double inv = 1.0 / ((double)M * C);
+  double sq = 0.0;
+  if (pix < M) {
+    const int n = (int)(pix / ((long)H * W));
+    const int rem = (int)(pix - (long)n * H * W), u = rem / W, v = rem - u * W;
+    const uint8_t f = flags ? flags[n] : 0;
+    const float* ap = a + ((long)(n * H + flip_idx(u, H, f & 1)) * W + flip_idx(v, W, f & 2)) * C;
+    const float* bp = b + pix * C;
+    float pa[16], pb[16];
+    float ma = -INFINITY, mb = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) {
+        pa[k] = ap[k];
+        pb[k] = bp[k];
+        ma = fmaxf(ma, pa[k]);
+        mb = fmaxf(mb, pb[k]);
+      }
+    float za = 0.f, zb = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) {
+        if (TSOFT) {
+          pa[k] = expf(pa[k] - ma);
+          za += pa[k];
+        }
+        pb[k] = expf(pb[k] - mb);
+        zb += pb[k];
+      }
+    const float gs = (float)(2.0 * weight * inv);
+    float gk[16], sgp = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) {
+        if (TSOFT) pa[k] /= za;
+        pb[k] /= zb;
+        const float d = pb[k] - pa[k];
+        sq += (double)d * d;
+        gk[k] = gs * d;
+        sgp = fmaf(gk[k], pb[k], sgp);
+      }
+    float* dp = db + pix * C;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) dp[k] = pb[k] * (gk[k] - sgp);
+  }
+  sq = block_sum_d(sq, sh);
+  ordered_total(sq, inv * weight, loss, partial, ticket);
+}
+
+// loss = weight / M * sum_pixels -sum_c p_c log(p_c + eps);  d/dx_k = p_k (g_k - sum_c p_c g_c),
+// g_c = -(log(p_c + eps) + p_c / (p_c + eps)) * weight / M
+__global__ void __launch_bounds__(256) entropy_kernel(const float* __restrict__ x, long M, int C, float eps, float weight,
+                                                      float* __restrict__ loss, float* __restrict__ dx,
+                                                      double* __restrict__ partial, unsigned int* __restrict__ ticket) {
+  __shared__ double sh[8];
+  const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const double inv = 1.0 / (double)M;
+  double ent = 0.0;
+  if (pix < M) {
+    const float* xp = x + pix * C;
+    float p[16];
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) {
+        p[k] = xp[k];
+        m = fmaxf(m, p[k]);
+      }
+    float z = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) {
+        p[k] = expf(p[k] - m);
+        z += p[k];
+      }
+    const float gs = (float)((double)weight * inv);
+    float g[16], sgp = 0.f, e = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) {
+        p[k] /= z;
+        const float q = p[k] + eps;
+        const float lq = logf(q);
+        e = fmaf(p[k], lq, e);
+        g[k] = -(lq + p[k] / q) * gs;
+        sgp = fmaf(g[k], p[k], sgp);
+      }
+    ent = -(double)e;
+    float* dp = dx + pix * C;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) dp[k] = p[k] * (g[k] - sgp);
+  }
+  ent = block_sum_d(ent, sh);
+  ordered_total(ent, inv * weight, loss, partial, ticket);
+}
+
+size_t pixel_workspace_bytes(long M) { return (size_t)((M + 255) / 256) * sizeof(double) + 64; }
+
+template <bool DECAY>
+void launch_ema(float* t, const float* s, size_t head, size_t n4, size_t n, float alpha, float oma, float keep, bool svec,
+                unsigned blocks, hipStream_t st) {
+  if (svec)
+    SPCL_LAUNCH((ema_update_kernel<DECAY, true>), dim3(blocks), dim3(256), 0, st, t, s, head, n4, n, alpha, oma, keep);
+  else
+    SPCL_LAUNCH((ema_update_kernel<DECAY, false>), dim3(blocks), dim3(256), 0, st, t, s, head, n4, n, alpha, oma, keep);
+}
+
+}  // namespace
+
+extern "C" int spcl_ema_update(float* teacher, const float* student, size_t n, double alpha, double decay, void* stream) {
+  SPCL_CHECK_ARG(teacher && student, "spcl_ema_update: null pointer");
+  SPCL_CHECK_ARG(n > 0, "spcl_ema_update: empty buffer");
+  SPCL_CHECK_ARG(((uintptr_t)teacher | (uintptr_t)student) % 4 == 0, "spcl_ema_update: buffers must be 4-byte aligned");
+  SPCL_CHECK_ARG(alpha >= 0.0 && alpha <= 1.0 && decay >= 0.0 && decay < 1.0, "spcl_ema_update: alpha in [0, 1], decay in [0, 1)");
+  const uintptr_t lo = (uintptr_t)teacher, hi = lo + n * sizeof(float), so = (uintptr_t)student;
+  SPCL_CHECK_ARG(so + n * sizeof(float) <= lo || so >= hi, "spcl_ema_update: teacher and student overlap");
+  size_t head = ((16 - (uintptr_t)teacher % 16) % 16) / 4;  // elements before the teacher's first 16-byte boundary
+  if (head > n) head = n;
+  const size_t n4 = (n - head) / 4;
+  const bool svec = (uintptr_t)(student + head) % 16 == 0;
+  size_t blocks = (n4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipStream_t st = (hipStream_t)stream;
+  spcl::prof_cost(12.0 * (double)n, 4.0 * (double)n);
+  const float af = (float)alpha, oma = (float)(1.0 - alpha), keep = (float)(1.0 - decay);
+  if (decay != 0.0) launch_ema<true>(teacher, student, head, n4, n, af, oma, keep, svec, (unsigned)blocks, st);
+  else launch_ema<false>(teacher, student, head, n4, n, af, oma, keep, svec, (unsigned)blocks, st);
+  SPCL_LAUNCH_CHECK("ema_update_kernel");
+  return SPCL_OK;
+}
+
+extern "C" size_t spcl_mt_softmax_mse_workspace_bytes(int N, int H, int W) { return pixel_workspace_bytes((long)N * H * W); }
+
+extern "C" int spcl_mt_softmax_mse(const float* teacher, const float* student_logits, int N, int C, int H, int W,
+                                   const uint8_t* flags_teacher, int teacher_mode, float weight, float* loss, float* dstudent,
+                                   void* ws, size_t ws_bytes, void* stream) {
+  SPCL_CHECK_ARG(teacher && student_logits && loss && dstudent && ws, "spcl_mt_softmax_mse: null pointer");
+  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C >= 1 && C <= 16, "spcl_mt_softmax_mse: bad shape (C <= 16)");
+  SPCL_CHECK_ARG((long)N * H * W < (1L << 31), "spcl_mt_softmax_mse: too many pixels");
+  SPCL_CHECK_ARG(teacher_mode == 0 || teacher_mode == 1, "spcl_mt_softmax_mse: teacher_mode %d is neither 0 (raw) nor 1 (softmax)",
+                 teacher_mode);
+  SPCL_CHECK_ARG(ws_bytes >= spcl_mt_softmax_mse_workspace_bytes(N, H, W), "spcl_mt_softmax_mse: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const long M = (long)N * H * W;
+  const int nblk = (int)((M + 255) / 256);
+  unsigned int* ticket = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double));
+  if (hipMemsetAsync(ticket, 0, sizeof(unsigned int), st) != hipSuccess) {
+    spcl::set_error("spcl_mt_softmax_mse: memset failed");
+    return SPCL_ELAUNCH;
+  }
+  spcl::prof_cost(3.0 * M * C * 4, 20.0 * M * C);
+  if (teacher_mode == 1)
+    SPCL_LAUNCH(mt_mse_kernel<true>, dim3(nblk), dim3(256), 0, st, teacher, student_logits, N, C, H, W, flags_teacher, weight,
+                loss, dstudent, (double*)ws, ticket);
+  else
+    SPCL_LAUNCH(mt_mse_kernel<false>, dim3(nblk), dim3(256), 0, st, teacher, student_logits, N, C, H, W, flags_teacher, weight,
+                loss, dstudent, (double*)ws, ticket);
+  SPCL_LAUNCH_CHECK("mt_mse_kernel");
+  return SPCL_OK;
+}
+
+extern "C" size_t spcl_entropy_softmax_workspace_bytes(int N, int H, int W) { return pixel_workspace_bytes((long)N * H * W); }
+
+extern "C" int spcl_entropy_softmax(const float* logits, int N, int C, int H, int W, float eps, float weight, float* loss,
+                                    float* dlogits, void* ws, size_t ws_bytes, void* stream) {
+  SPCL_CHECK_ARG(logits && loss && dlogits && ws, "spcl_entropy_softmax: null pointer");
+  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C >= 1 && C <= 16, "spcl_entropy_softmax: bad shape (C <= 16)");
+  SPCL_CHECK_ARG((long)N * H * W < (1L << 31), "spcl_entropy_softmax: too many pixels");
+  SPCL_CHECK_ARG(eps >= 0.f, "spcl_entropy_softmax: negative eps");
+  SPCL_CHECK_ARG(ws_bytes >= spcl_entropy_softmax_workspace_bytes(N, H, W), "spcl_entropy_softmax: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const long M = (long)N * H * W;
+  const int nblk = (int)((M + 255) / 256);
+  unsigned int* ticket = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double));
+  if (hipMemsetAsync(ticket, 0, sizeof(unsigned int), st) != hipSuccess) {
+    spcl::set_error("spcl_entropy_softmax: memset failed");
+    return SPCL_ELAUNCH;
+  }
+  spcl::prof_cost(2.0 * M * C * 4, 30.0 * M * C);
+  SPCL_LAUNCH(entropy_kernel, dim3(nblk), dim3(256), 0, st, logits, M, C, eps, weight, loss, dlogits, (double*)ws, ticket);
+  SPCL_LAUNCH_CHECK("entropy_kernel");
+  return SPCL_OK;
+}

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_float, c_int
+from ctypes import c_double, c_float, c_int
 
 import torch
 
@@ -2626,3 +2626,86 @@ class _ConsistencyFn(torch.autograd.Function):
 def consistency_softmax_mse(a, b, weight=1.0, flags=None):
     """consistency.py:30-35: ``weight * mse(softmax(flip(a)).detach(), softmax(b))`` of logical [N, C, H, W] logits"""
     return _ConsistencyFn.apply(a, b, flags, float(weight))
+
+
+# ------------------------------------------------------------------- mean teacher / entropy minimisation (csrc/semi_reg.hip)
+def ema_update_(teacher_flat, student_flat, alpha, decay=0.0):
+    """in place ``teacher = (alpha * teacher + (1 - alpha) * student) * (1 - decay)`` over two f32 tensors of one size, each
+    dense in memory (mt.py:54 -> deepclustering2 ``ema_updater``), one launch; any 4-byte-aligned view will do"""
+    _n.require_gpu(teacher_flat, student_flat)
+    t, s = teacher_flat.detach(), student_flat.detach()
+    if t.dtype != torch.float32 or s.dtype != torch.float32 or t.numel() != s.numel() or t.device != s.device:
+        raise ValueError(f"ema_update_: two f32 tensors of one size on one device, got {t.dtype} {tuple(t.shape)} on {t.device} "
+                         f"and {s.dtype} {tuple(s.shape)} on {s.device}")
+    if not (t.is_contiguous() and s.is_contiguous()):
+        raise ValueError("ema_update_: both tensors must be contiguous (a copy would not be updated in place)")
+    if t.numel() > 0:
+        _n.call("spcl_ema_update", _n.ptr(t), _n.ptr(s), t.numel(), c_double(alpha), c_double(decay), _n.stream())
+    return teacher_flat
+
+
+class _MTSoftmaxMSEFn(torch.autograd.Function):
+    """``weight * MSELoss(flip(T), softmax(student_logits))`` in one launch, ``T`` the teacher's output or its softmax; the
+    gradient w.r.t. the student's logits for a unit upstream gradient is written by the same launch (the teacher gets none)."""
+
+    @staticmethod
+    def forward(ctx, teacher, student, flags, weight, mode):
+        _n.require_gpu(teacher, student)
+        ts, ss = _class_map_storage(teacher.detach()), _class_map_storage(student.detach())
+        if ts.shape != ss.shape:
+            raise AssertionError(f"class maps {tuple(ts.shape)} / {tuple(ss.shape)} differ")
+        N, H, W, C = ss.shape
+        dev = ss.device
+        fl = _flip_flags_arg(flags, N, dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        ds = torch.empty_like(ss)
+        ws = torch.empty(_n.call("spcl_mt_softmax_mse_workspace_bytes", N, H, W), dtype=torch.uint8, device=dev)
+        _n.call("spcl_mt_softmax_mse", _n.ptr(ts), _n.ptr(ss), N, C, H, W, _n.ptr(fl), int(mode), c_float(weight),
+                _n.ptr(loss), _n.ptr(ds), _n.ptr(ws), ws.numel(), _n.stream())
+        ctx.save_for_backward(ds)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (ds,) = ctx.saved_tensors
+        if is_unit_gradient(g):
+            return None, ds.permute(0, 3, 1, 2), None, None, None
+        return None, (ds * g.detach().float()).permute(0, 3, 1, 2), None, None, None
+
+
+def mt_softmax_mse(teacher, student_logits, weight=1.0, flags=None, teacher_softmax=False):
+    """mt.py:48-52: ``weight * mse(flip(teacher), softmax(student_logits))`` of logical [N, C, H, W] maps; with
+    ``teacher_softmax`` the teacher's map is soft-maxed first (_mixins.py:147)"""
+    return _MTSoftmaxMSEFn.apply(teacher, student_logits, flags, float(weight), 1 if teacher_softmax else 0)
+
+
+class _EntropySoftmaxFn(torch.autograd.Function):
+    """``weight * Entropy(eps)(softmax(logits))`` in one launch; the gradient w.r.t. the logits for a unit upstream gradient
+    is written by the same launch."""
+
+    @staticmethod
+    def forward(ctx, logits, eps, weight):
+        _n.require_gpu(logits)
+        ls = _class_map_storage(logits.detach())
+        N, H, W, C = ls.shape
+        dev = ls.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dl = torch.empty_like(ls)
+        ws = torch.empty(_n.call("spcl_entropy_softmax_workspace_bytes", N, H, W), dtype=torch.uint8, device=dev)
+        _n.call("spcl_entropy_softmax", _n.ptr(ls), N, C, H, W, c_float(eps), c_float(weight), _n.ptr(loss), _n.ptr(dl),
+                _n.ptr(ws), ws.numel(), _n.stream())
+        ctx.save_for_backward(dl)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        if is_unit_gradient(g):
+            return dl.permute(0, 3, 1, 2), None, None
+        return (dl * g.detach().float()).permute(0, 3, 1, 2), None, None
+
+
+def entropy_softmax(logits, eps=1e-16, weight=1.0):
+    """entmin.py:30-31: ``weight * mean over pixels of -sum_c p_c log(p_c + eps)``, ``p = softmax(logits)``, of logical
+    [N, C, H, W] logits"""
+    return _EntropySoftmaxFn.apply(logits, float(eps), float(weight))

@@ -4,7 +4,9 @@ Contract (hook_creator.py:10-28): ``InfonceParams`` builds plain InfoNCE hooks, 
 (they also get the trainer's ``max_epoch`` for their age-parameter schedule); both receive ``Data.name``.
 ``DiscreteMIConsistencyParams`` (the UDA-IIC baseline) builds the discrete-MI + consistency hooks
 (``create_discrete_mi_consistency_hook``) outside pre-training; during pre-training the reference raises RuntimeError for
-it and so does this mirror."""
+it and so does this mirror.  ``MeanTeacherParameters`` (keys of config/specific/mt.yaml) and ``EntropyMinParameters``
+(``weight``) build the mean-teacher and entropy-minimisation hooks under the same rule: the reference's
+``create_hook_from_config`` notes that pre-training accepts no mean teacher (hook_creator.py:6)."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -13,6 +15,11 @@ _SECTIONS = (
     ("SPInfonceParams", "create_sp_infonce_hooks", True),
 )
 _BASELINE_SECTION = "DiscreteMIConsistencyParams"
+# semi-supervised baselines: section -> (factory, does the factory take the model?)
+_SEMI_SECTIONS = (
+    ("MeanTeacherParameters", "create_mean_teacher_hook", True),
+    ("EntropyMinParameters", "create_entropy_min_hook", False),
+)
 
 
 def create_hook_from_config(model, config, is_pretrain=False):
@@ -28,4 +35,10 @@ def create_hook_from_config(model, config, is_pretrain=False):
         if is_pretrain:
             raise RuntimeError(f"{_BASELINE_SECTION} are not supported for pretrain stage")
         built.append(_hooks.create_discrete_mi_consistency_hook(model=model, **config[_BASELINE_SECTION]))
+    for section, factory, wants_model in _SEMI_SECTIONS:
+        if section in config:
+            if is_pretrain:
+                raise RuntimeError(f"{section} are not supported for pretrain stage")
+            extra = {"model": model} if wants_model else {}
+            built.append(getattr(_hooks, factory)(**extra, **config[section]))
     return built

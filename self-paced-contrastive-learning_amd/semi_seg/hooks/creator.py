@@ -1,14 +1,19 @@
 """Mirror of the factories in ``semi_seg/hooks/creator.py``: ``feature_until_from_hooks`` (:23-29),
 ``create_infonce_hooks`` (:69-99) and ``create_sp_infonce_hooks`` (:102-124) -- one hook per (feature, weight,
 contrast_on) triple combined into one TrainerHook -- and the UDA-IIC factories ``create_consistency_hook`` (:32-33),
-``create_discrete_mi_hooks`` (:36-47) and ``create_discrete_mi_consistency_hook`` (:50-66)."""
+``create_discrete_mi_hooks`` (:36-47) and ``create_discrete_mi_consistency_hook`` (:50-66).  ``create_mean_teacher_hook`` and
+``create_entropy_min_hook`` have no counterpart there: the reference builds those two baselines in their trainers
+(semi_seg/trainers/trainer.py:227-271, from ``EntropyMinParameters`` / ``MeanTeacherParameters``); the hook names are its
+trainer-registry keys (semi_seg/trainers/__init__.py:11-12)."""
 from typing import List, Union
 
 from ...contrastyou.hooks.base import CombineTrainerHook
 from ..arch.unet import sort_arch
 from .consistency import ConsistencyTrainerHook
 from .discretemi import DiscreteMITrainHook
+from .entmin import EntropyMinTrainerHook
 from .infonce import INFONCEHook, SelfPacedINFONCEHook, decoder_names
+from .mt import MeanTeacherTrainerHook
 
 
 def _listify(v, n):
@@ -95,3 +100,14 @@ def create_discrete_mi_consistency_hook(*, model, feature_names: Union[str, List
                                                 model=model)
     consistency_hook = create_consistency_hook(weight=consistency_weight)
     return CombineTrainerHook(discrete_mi_hook, consistency_hook)
+
+
+def create_mean_teacher_hook(*, model, weight: float, alpha: float = 0.999, weight_decay: float = 1e-5, name: str = "mse"):
+    """``MeanTeacherParameters`` of config/specific/mt.yaml: ``name`` is the teacher criterion (only ``mse`` is mirrored)"""
+    if name != "mse":
+        raise NotImplementedError(f"mean teacher criterion {name!r}: only 'mse' is mirrored")
+    return MeanTeacherTrainerHook(name="meanteacher", weight=weight, model=model, alpha=alpha, weight_decay=weight_decay)
+
+
+def create_entropy_min_hook(*, weight: float):
+    return EntropyMinTrainerHook(name="entropy", weight=weight)

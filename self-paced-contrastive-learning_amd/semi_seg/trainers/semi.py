@@ -35,7 +35,9 @@ class SemiTrainer(FineTuneTrainer):
         self.__hooks__.to(self._device)
         _ddp.broadcast_state(self._model, self.__hooks__)
         params = [p for p in self._model.parameters() if p.requires_grad]
-        hook_params = [p for h in self.__hooks__ for p in h.parameters()]
+        # (requires_grad: a hook may hold modules that are not trained -- the mean teacher's detached copy of the model --,
+        # which travel with ``__hooks__`` (device, broadcast, checkpoint) but are no business of the optimizer)
+        hook_params = [p for h in self.__hooks__ for p in h.parameters() if p.requires_grad]
         self._flat = _ddp.FlatParams(params + hook_params)
         self._optimizer = build_optimizer(self._optim_name, self._flat.param, self._optim_cfg)
         self._scheduler = None
