@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 11
+#define SPCL_ABI_VERSION 12
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -847,6 +847,32 @@ int spcl_mt_softmax_mse(const float* teacher, const float* student_logits, int N
 size_t spcl_entropy_softmax_workspace_bytes(int N, int H, int W);
 int spcl_entropy_softmax(const float* logits, int N, int C, int H, int W, float eps, float weight, float* loss, float* dlogits,
                          void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- mix-up baseline (csrc/semi_reg.hip) -------------------------
+ * Replaces the arithmetic of semi_seg/hooks/mixup.py:19-32 (mixup_data) and :66-75 (one-hot targets, concatenations, softmax,
+ * KL_div) of the reference.  Both entry points read the VIRTUAL concatenation of two batches of B = N2 / 2 samples (sample n
+ * is the first batch's n for n < B, the second's n - B otherwise; nothing is concatenated) and a device permutation
+ * index[N2] (int32) of its samples.  lam / oml: the f32 roundings of the host's float64 lam and 1 - lam.  The caller checks
+ * on the host that every index entry lies in [0, N2) (functional.MixupPlan does); for an entry outside it the kernels pair the
+ * sample with itself, so that no content of the buffer makes them read outside their inputs.
+ *
+ *   spcl_mixup_images: out[n] = fl(fl(lam * x[n]) + fl(oml * x[index[n]])) over f32 samples of per_sample elements
+ *                    (mixup.py:30): three roundings in the order torch evaluates the expression on an f32 tensor, never
+ *                    contracted to a fused multiply-add -- the result is torch's bit for bit.  One launch, 12 bytes per
+ *                    element; 16-byte accesses when per_sample % 4 == 0 and the three base pointers are 16-byte aligned,
+ *                    4-byte ones otherwise.  out [N2 * per_sample] must not overlap either input.
+ *   spcl_mixup_kl_onehot: weight * KL_div(eps)(softmax(logits), lam * onehot(y) + oml * onehot(y[index])), the mean over the
+ *                    N2*H*W pixels of sum_c -t_c log((p_c + eps) / (t_c + eps)) (mixup.py:31,66-75), y the two int64 label maps
+ *                    [B, H, W], logits [N2, H, W, C] f32 (C <= 16); t_c is built in f32 as torch builds mixed_y (fl(lam + oml)
+ *                    where the two labels agree).  Labels are compared with the class index only: one outside [0, C) selects
+ *                    no class.  dlogits = the gradient for a unit upstream gradient; ws: spcl_mixup_kl_workspace_bytes(N2,
+ *                    H, W).  A fixed-order sum as above: bitwise reproducible. */
+int spcl_mixup_images(const float* image, const float* image_tf, const int* index, int N2, size_t per_sample, float lam,
+                      float oml, float* out, void* stream);
+size_t spcl_mixup_kl_workspace_bytes(int N2, int H, int W);
+int spcl_mixup_kl_onehot(const float* logits, const int64_t* target, const int64_t* target_tf, const int* index, int N2, int C,
+                         int H, int W, float lam, float oml, float eps, float weight, float* loss, float* dlogits, void* ws,
+                         size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -37,9 +37,11 @@ _MIRRORED = {
     "semi_seg.hooks.consistency": "semi_seg.hooks.consistency",
     "semi_seg.hooks.mt": "semi_seg.hooks.mt",
     "semi_seg.hooks.entmin": "semi_seg.hooks.entmin",
+    "semi_seg.hooks.mixup": "semi_seg.hooks.mixup",
     "semi_seg.epochers": "semi_seg.epochers",
     "semi_seg.epochers.new_pretrain": "semi_seg.epochers.pretrain",
     "semi_seg.epochers.new_epocher": "semi_seg.epochers.finetune",
+    "semi_seg.epochers.new_comparable": "semi_seg.epochers.mixup",
     "semi_seg.epochers.helper": "semi_seg.epochers.helper",
     "semi_seg.trainers": "semi_seg.trainers",
     "semi_seg.trainers.new_pretrain": "semi_seg.trainers.pretrain",

@@ -1,4 +1,5 @@
-// Regularisers of the mean-teacher and entropy-minimisation baselines (semi_seg/hooks/mt.py, semi_seg/hooks/entmin.py).
+// Regularisers of the mean-teacher, entropy-minimisation and mix-up baselines (semi_seg/hooks/mt.py, semi_seg/hooks/entmin.py,
+// semi_seg/hooks/mixup.py).
 //
 //   spcl_ema_update:      the teacher's exponential moving average over ONE flat f32 buffer (mt.py:54 -> deepclustering2
 //                         ema_updater: mul_(alpha), add_((1 - alpha) * s), mul_(1 - decay) per parameter tensor, ~180 launches
@@ -14,7 +15,18 @@
 //                         raw output (mt.py:49-52 applies no softmax) or its softmax (the older _mixins.py:147).
 //   spcl_entropy_softmax: weight * mean over pixels of -sum_c p_c log(p_c + eps), p = softmax(logits), and its gradient.
 //
-// Both criteria: one thread per pixel (C <= 16 channels in registers), per-workgroup double partials, the last workgroup
+//
+// and of the mix-up baseline (semi_seg/hooks/mixup.py), over the VIRTUAL concatenation of two batches of B samples (sample n
+// is a[n] for n < B, b[n - B] otherwise; nothing is concatenated) and a permutation index of its 2B samples:
+//   spcl_mixup_images:    out[n] = lam * x[n] + (1 - lam) * x[index[n]] (mixup.py:30), three f32 roundings in torch's order
+//                         (two products, one sum: never contracted to a fused multiply-add), bit for bit what torch computes.
+//                         12 bytes per element, no reuse: bandwidth-bound.  One grid row per output sample, a capped grid
+//                         stride in x; 16-byte loads / stores when the sample size is a multiple of four elements and the three
+//                         base pointers are 16-byte aligned, 4-byte ones otherwise.
+//   spcl_mixup_kl_onehot: weight * KL_div(eps)(softmax(logits), lam * onehot(y) + (1 - lam) * onehot(y[index])) and its
+//                         gradient (mixup.py:31,66-75): the soft target is built per pixel from two labels, never stored.
+//
+// The criteria: one thread per pixel (C <= 16 channels in registers), per-workgroup double partials, the last workgroup
 // to take a ticket sums them in index order and resets the ticket: loss and gradient are bitwise reproducible.
 #include "common.hpp"
 
@@ -195,6 +207,113 @@ __global__ void __launch_bounds__(256) entropy_kernel(const float* __restrict__ 
   ordered_total(ent, inv * weight, loss, partial, ticket);
 }
 
+// sample n of the virtual concatenation (a, b) of two batches of B samples, per elements each
+template <typename T>
+__device__ __forceinline__ const T* cat_sample(const T* a, const T* b, int n, int B, size_t per) {
+  return n < B ? a + (size_t)n * per : b + (size_t)(n - B) * per;
+}
+
+// an index outside [0, N2) (the callers refuse it on the host before the copy) selects the sample itself: no read outside
+// the inputs whatever the buffer holds
+__device__ __forceinline__ int mix_partner(const int* __restrict__ index, int n, int N2) {
+  const int j = index[n];
+  return (unsigned)j < (unsigned)N2 ? j : n;
+}
+
+// fl(fl(lam * u) + fl(oml * v)): the roundings of torch's `lam * x + (1 - lam) * x[index]` on an f32 tensor.  hipcc contracts
+// a product and a sum into one fused multiply-add by default (and sees through __fmul_rn / __fadd_rn, which are plain
+// operators compiled under that default), which rounds twice: the pragma keeps the three operations of this block apart.
+__device__ __forceinline__ float mix_one(float u, float v, float lam, float oml) {
+#pragma clang fp contract(off)
+  const float a = lam * u;
+  const float b = oml * v;
+  return a + b;
+}
+
+// blockIdx.y = output sample; VEC: per % 4 == 0 and every base pointer 16-byte aligned (then every sample is)
+template <bool VEC>
+__global__ void __launch_bounds__(256) mixup_images_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                           const int* __restrict__ index, int B, size_t per, float lam,
+                                                           float oml, float* __restrict__ out) {
+  const int n = blockIdx.y, N2 = 2 * B;
+  const float* u = cat_sample(a, b, n, B, per);
+  const float* v = cat_sample(a, b, mix_partner(index, n, N2), B, per);
+  float* o = out + (size_t)n * per;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  if (VEC) {
+    const size_t per4 = per / 4;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < per4; i += stride) {
+      const f32x4 x = reinterpret_cast<const f32x4*>(u)[i], y = reinterpret_cast<const f32x4*>(v)[i];
+      f32x4 r;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) r[e] = mix_one(x[e], y[e], lam, oml);
+      reinterpret_cast<f32x4*>(o)[i] = r;
+    }
+  } else {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += stride) o[i] = mix_one(u[i], v[i], lam, oml);
+  }
+}
+
+// loss = weight / M * sum_pixels sum_c -t_c log((p_c + eps) / (t_c + eps)), t_c = (c == la ? lam : 0) + (c == lb ? oml : 0) with
+// la the pixel's own label and lb the label of the same pixel in sample index[n];  d/dx_k = p_k (g_k - sum_c g_c p_c),
+// g_c = -(weight / M) t_c / (p_c + eps), evaluated as -(weight / M) (t_k r_k - p_k sum_c t_c r_c) with r_c = p_c / (p_c + eps)
+// <= 1 (the same value; no quotient by a vanishing p_c + eps is ever formed).  Labels are compared with c only.
+__global__ void __launch_bounds__(256) mixup_kl_kernel(const float* __restrict__ x, const int64_t* __restrict__ ya,
+                                                       const int64_t* __restrict__ yb, const int* __restrict__ index, int B,
+                                                       int HW, int C, float lam, float oml, float eps, float weight,
+                                                       float* __restrict__ loss, float* __restrict__ dx,
+                                                       double* __restrict__ partial, unsigned int* __restrict__ ticket) {
+  __shared__ double sh[8];
+  const int N2 = 2 * B;
+  const long M = (long)N2 * HW;
+  const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const double inv = 1.0 / (double)M;
+  double kl = 0.0;
+  if (pix < M) {
+    const int n = (int)(pix / HW), rem = (int)(pix - (long)n * HW);
+    const long la = cat_sample(ya, yb, n, B, (size_t)HW)[rem];
+    const long lb = cat_sample(ya, yb, mix_partner(index, n, N2), B, (size_t)HW)[rem];
+    const float* xp = x + pix * C;
+    float p[16];
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) {
+        p[k] = xp[k];
+        m = fmaxf(m, p[k]);
+      }
+    float z = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) {
+        p[k] = expf(p[k] - m);
+        z += p[k];
+      }
+    const float gs = (float)((double)weight * inv);
+    float tr[16], str = 0.f, e = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) {
+        p[k] /= z;
+        const float t = (k == la ? lam : 0.f) + (k == lb ? oml : 0.f);
+        const float q = p[k] + eps;
+        tr[k] = 0.f;
+        if (t != 0.f) {  // (a class outside the target adds -0 * log(..) = 0 and no gradient)
+          e = fmaf(t, logf(q / (t + eps)), e);
+          tr[k] = t * (p[k] / q);
+          str += tr[k];
+        }
+      }
+    kl = -(double)e;
+    float* dp = dx + pix * C;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) dp[k] = -gs * (tr[k] - p[k] * str);
+  }
+  kl = block_sum_d(kl, sh);
+  ordered_total(kl, inv * weight, loss, partial, ticket);
+}
+
 size_t pixel_workspace_bytes(long M) { return (size_t)((M + 255) / 256) * sizeof(double) + 64; }
 
 template <bool DECAY>
@@ -281,5 +400,55 @@ extern "C" int spcl_entropy_softmax(const float* logits, int N, int C, int H, in
   spcl::prof_cost(2.0 * M * C * 4, 30.0 * M * C);
   SPCL_LAUNCH(entropy_kernel, dim3(nblk), dim3(256), 0, st, logits, M, C, eps, weight, loss, dlogits, (double*)ws, ticket);
   SPCL_LAUNCH_CHECK("entropy_kernel");
+  return SPCL_OK;
+}
+
+extern "C" int spcl_mixup_images(const float* image, const float* image_tf, const int* index, int N2, size_t per_sample,
+                                 float lam, float oml, float* out, void* stream) {
+  SPCL_CHECK_ARG(image && image_tf && index && out, "spcl_mixup_images: null pointer");
+  SPCL_CHECK_ARG(N2 > 0 && N2 % 2 == 0 && N2 <= 65534 && per_sample > 0, "spcl_mixup_images: bad shape (N2 = 2 B <= 65534)");
+  SPCL_CHECK_ARG(((uintptr_t)image | (uintptr_t)image_tf | (uintptr_t)out) % 4 == 0,
+                 "spcl_mixup_images: buffers must be 4-byte aligned");
+  const int B = N2 / 2;
+  const uintptr_t half = (uintptr_t)B * per_sample * sizeof(float), lo = (uintptr_t)out, hi = lo + 2 * half;
+  for (const float* in : {image, image_tf})
+    SPCL_CHECK_ARG((uintptr_t)in + half <= lo || (uintptr_t)in >= hi, "spcl_mixup_images: out overlaps an input");
+  const bool vec = per_sample % 4 == 0 && ((uintptr_t)image | (uintptr_t)image_tf | (uintptr_t)out) % 16 == 0;
+  const size_t work = vec ? per_sample / 4 : per_sample;
+  size_t bx = (work + 255) / 256, cap = 2048 / (size_t)N2;  // at most 2048 workgroups of 256 in all (8 per CU), stride beyond
+  if (cap < 1) cap = 1;
+  if (bx > cap) bx = cap;
+  hipStream_t st = (hipStream_t)stream;
+  spcl::prof_cost(12.0 * (double)N2 * (double)per_sample, 3.0 * (double)N2 * (double)per_sample);
+  const dim3 grid((unsigned)bx, (unsigned)N2);
+  if (vec) SPCL_LAUNCH(mixup_images_kernel<true>, grid, dim3(256), 0, st, image, image_tf, index, B, per_sample, lam, oml, out);
+  else SPCL_LAUNCH(mixup_images_kernel<false>, grid, dim3(256), 0, st, image, image_tf, index, B, per_sample, lam, oml, out);
+  SPCL_LAUNCH_CHECK("mixup_images_kernel");
+  return SPCL_OK;
+}
+
+extern "C" size_t spcl_mixup_kl_workspace_bytes(int N2, int H, int W) { return pixel_workspace_bytes((long)N2 * H * W); }
+
+extern "C" int spcl_mixup_kl_onehot(const float* logits, const int64_t* target, const int64_t* target_tf, const int* index,
+                                    int N2, int C, int H, int W, float lam, float oml, float eps, float weight, float* loss,
+                                    float* dlogits, void* ws, size_t ws_bytes, void* stream) {
+  SPCL_CHECK_ARG(logits && target && target_tf && index && loss && dlogits && ws, "spcl_mixup_kl_onehot: null pointer");
+  SPCL_CHECK_ARG(N2 > 0 && N2 % 2 == 0 && H > 0 && W > 0 && C >= 1 && C <= 16,
+                 "spcl_mixup_kl_onehot: bad shape (N2 = 2 B, C <= 16)");
+  SPCL_CHECK_ARG((long)N2 * H * W < (1L << 31), "spcl_mixup_kl_onehot: too many pixels");
+  SPCL_CHECK_ARG(eps >= 0.f, "spcl_mixup_kl_onehot: negative eps");
+  SPCL_CHECK_ARG(ws_bytes >= spcl_mixup_kl_workspace_bytes(N2, H, W), "spcl_mixup_kl_onehot: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const long M = (long)N2 * H * W;
+  const int nblk = (int)((M + 255) / 256);
+  unsigned int* ticket = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double));
+  if (hipMemsetAsync(ticket, 0, sizeof(unsigned int), st) != hipSuccess) {
+    spcl::set_error("spcl_mixup_kl_onehot: memset failed");
+    return SPCL_ELAUNCH;
+  }
+  spcl::prof_cost(2.0 * M * C * 4 + 16.0 * M, 30.0 * M * C);
+  SPCL_LAUNCH(mixup_kl_kernel, dim3(nblk), dim3(256), 0, st, logits, target, target_tf, index, N2 / 2, H * W, C, lam, oml, eps,
+              weight, loss, dlogits, (double*)ws, ticket);
+  SPCL_LAUNCH_CHECK("mixup_kl_kernel");
   return SPCL_OK;
 }

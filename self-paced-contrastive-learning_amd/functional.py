@@ -2709,3 +2709,112 @@ def entropy_softmax(logits, eps=1e-16, weight=1.0):
     """entmin.py:30-31: ``weight * mean over pixels of -sum_c p_c log(p_c + eps)``, ``p = softmax(logits)``, of logical
     [N, C, H, W] logits"""
     return _EntropySoftmaxFn.apply(logits, float(eps), float(weight))
+
+
+# ------------------------------------------------------------------------------------------------ mix-up (csrc/semi_reg.hip)
+class MixupPlan:
+    """One mix-up draw (mixup.py:19-32) for a batch of B labelled samples and their second views: ``lam`` (the host's float64),
+    ``pair`` = the f32 roundings of ``(lam, 1 - lam)`` the kernels compute with, ``n2`` = 2B and ``index`` = the permutation
+    of the 2B samples as int32 on ``device`` (a pinned host buffer and an asynchronous copy: no synchronisation).
+
+    ``perm``: a host integer sequence or CPU tensor, as ``torch.randperm(2B)`` returns it.  Checked HERE, on the host: an even
+    length and every entry in [0, 2B) -- the kernels index their inputs by it."""
+
+    def __init__(self, perm, lam, device):
+        if isinstance(perm, torch.Tensor):
+            if perm.is_cuda or perm.dim() != 1 or perm.is_floating_point() or perm.is_complex() or perm.dtype == torch.bool:
+                raise ValueError("MixupPlan: `perm` must be a 1-d integer tensor on the CPU")
+            entries = perm.tolist()
+        else:
+            entries = list(perm)
+            if any(isinstance(v, bool) or int(v) != v for v in entries):
+                raise ValueError("MixupPlan: `perm` must hold integers")
+            entries = [int(v) for v in entries]
+        n2 = len(entries)
+        if n2 == 0 or n2 % 2 != 0:
+            raise ValueError(f"MixupPlan: `perm` must index two batches of one size, got {n2} entries")
+        if min(entries) < 0 or max(entries) >= n2:
+            raise ValueError(f"MixupPlan: every entry of `perm` must lie in [0, {n2}), got {min(entries)} .. {max(entries)}")
+        self.lam = float(lam)
+        self.pair = (float(torch.tensor(self.lam, dtype=torch.float32)), float(torch.tensor(1 - self.lam, dtype=torch.float32)))
+        self.n2 = n2
+        host = torch.tensor(entries, dtype=torch.int32)
+        device = torch.device(device)
+        self.index = host.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else host
+
+
+def _mixup_plan_arg(plan, n2, device):
+    if not isinstance(plan, MixupPlan):
+        raise TypeError(f"a MixupPlan is expected, got {type(plan).__name__}")
+    if plan.n2 != n2:
+        raise ValueError(f"the plan permutes {plan.n2} samples, the two batches hold {n2}")
+    if plan.index.device != device:
+        raise RuntimeError(f"the plan's index lives on {plan.index.device}, the tensors on {device}")
+    return plan.index
+
+
+def mixup_images(image, image_tf, plan):
+    """mixup.py:30,70 in one launch: ``lam * x + (1 - lam) * x[index]`` over ``x = cat([image, image_tf])`` (never built) ->
+    [2B, Cin, H, W] f32, bit for bit what torch computes on f32 tensors.  No autograd: the inputs are data."""
+    _n.require_gpu(image, image_tf)
+    a, b = image.detach(), image_tf.detach()
+    if a.shape != b.shape or a.dim() < 2 or a.dtype != torch.float32 or b.dtype != torch.float32 or a.device != b.device:
+        raise ValueError(f"mixup_images: two f32 batches of one shape on one device, got {a.dtype} {tuple(a.shape)} on "
+                         f"{a.device} and {b.dtype} {tuple(b.shape)} on {b.device}")
+    a, b = a.contiguous(), b.contiguous()
+    B = a.shape[0]
+    index = _mixup_plan_arg(plan, 2 * B, a.device)
+    out = torch.empty((2 * B,) + tuple(a.shape[1:]), dtype=torch.float32, device=a.device)
+    per = a.numel() // B if B else 0
+    if per > 0:
+        lam, oml = plan.pair
+        _n.call("spcl_mixup_images", _n.ptr(a), _n.ptr(b), _n.ptr(index), 2 * B, per, c_float(lam), c_float(oml), _n.ptr(out),
+                _n.stream())
+    return out
+
+
+def _label_map_arg(t, B, H, W, name):
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t.squeeze(1)
+    if tuple(t.shape) != (B, H, W):
+        raise ValueError(f"mixup_kl_onehot: `{name}` must be [{B}, 1, {H}, {W}] or [{B}, {H}, {W}], got {tuple(t.shape)}")
+    if t.dtype != torch.int64:
+        t = t.long()
+    return t.contiguous()
+
+
+class _MixupKLFn(torch.autograd.Function):
+    """``weight * KL_div(eps)(softmax(logits), lam * onehot(y) + (1 - lam) * onehot(y[index]))`` in one launch; the gradient
+    w.r.t. the logits for a unit upstream gradient is written by the same launch."""
+
+    @staticmethod
+    def forward(ctx, logits, target, target_tf, plan, eps, weight):
+        _n.require_gpu(logits, target, target_tf)
+        ls = _class_map_storage(logits.detach())
+        N2, H, W, C = ls.shape
+        dev = ls.device
+        index = _mixup_plan_arg(plan, N2, dev)
+        ya = _label_map_arg(target.detach(), N2 // 2, H, W, "target")
+        yb = _label_map_arg(target_tf.detach(), N2 // 2, H, W, "target_tf")
+        lam, oml = plan.pair
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dl = torch.empty_like(ls)
+        ws = torch.empty(_n.call("spcl_mixup_kl_workspace_bytes", N2, H, W), dtype=torch.uint8, device=dev)
+        _n.call("spcl_mixup_kl_onehot", _n.ptr(ls), _n.ptr(ya), _n.ptr(yb), _n.ptr(index), N2, C, H, W, c_float(lam),
+                c_float(oml), c_float(eps), c_float(weight), _n.ptr(loss), _n.ptr(dl), _n.ptr(ws), ws.numel(), _n.stream())
+        ctx.save_for_backward(dl)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        if is_unit_gradient(g):
+            return dl.permute(0, 3, 1, 2), None, None, None, None, None
+        return (dl * g.detach().float()).permute(0, 3, 1, 2), None, None, None, None, None
+
+
+def mixup_kl_onehot(logits, target, target_tf, plan, eps=1e-16, weight=1.0):
+    """mixup.py:31,66-75: ``weight * KL_div(eps)(softmax(logits), mixed_y)`` of logical [2B, C, H, W] logits, ``mixed_y`` the
+    plan's blend of the one-hot maps of ``cat([target, target_tf])`` and of their permutation (never built); targets
+    [B, 1, H, W] or [B, H, W] integer label maps"""
+    return _MixupKLFn.apply(logits, target, target_tf, plan, float(eps), float(weight))

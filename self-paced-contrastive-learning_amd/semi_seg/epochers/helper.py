@@ -53,6 +53,31 @@ class FixRandomSeed:
         np.random.set_state(self._np_state)
 
 
+class FixAllSeed:
+    """Context manager: seed python's, numpy's and torch's CPU generators, restore the three states on exit -- what the mix-up
+    hook draws under (``contrastyou.utils.fix_all_seed_within_context`` at semi_seg/hooks/mixup.py:69: ``np.random.beta``, then
+    ``torch.randperm`` on the CPU generator).  The reference also reseeds and restores the device generators and sets
+    ``PYTHONHASHSEED``: nothing inside this project's uses of the context draws from a device generator, so leaving them alone
+    gives the same draws and the same state afterwards; the environment variable is a side effect this mirror does not copy."""
+
+    def __init__(self, seed):
+        self._seed = seed
+
+    def __enter__(self):
+        import numpy as np
+        self._state, self._np_state, self._torch_state = random.getstate(), np.random.get_state(), torch.get_rng_state()
+        random.seed(self._seed)
+        np.random.seed(self._seed % (2 ** 32))
+        torch.default_generator.manual_seed(self._seed)  # (the CPU generator alone; torch.manual_seed seeds the devices' too)
+        return self
+
+    def __exit__(self, *a):
+        import numpy as np
+        random.setstate(self._state)
+        np.random.set_state(self._np_state)
+        torch.set_rng_state(self._torch_state)
+
+
 class TensorRandomFlip:
     """Flip a [C,H,W] sample along each of ``axis`` independently when u < threshold (u ~ python ``random``)."""
 

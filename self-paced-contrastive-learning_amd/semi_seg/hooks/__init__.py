@@ -6,3 +6,4 @@ from .consistency import ConsistencyTrainerHook  # noqa: F401
 from .discretemi import DiscreteMITrainHook  # noqa: F401
 from .entmin import EntropyMinTrainerHook  # noqa: F401
 from .mt import MeanTeacherTrainerHook  # noqa: F401
+from .mixup import MixUpHook  # noqa: F401

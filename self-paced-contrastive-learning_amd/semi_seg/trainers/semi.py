@@ -1,11 +1,13 @@
 """Mirror of ``SemiTrainer`` (semi_seg/trainers/new_trainer.py:17-56): ``FineTuneTrainer``'s epoch loop, evaluation and
 best / last checkpoints with the hook registry of the pre-train trainer -- ``register_hooks`` before ``init()``, one flat
 parameter over model + hook parameters, ``__hooks__`` in the checkpoint -- and ``SemiSupervisedEpocher`` as the training
-epocher (``two_stage`` / ``disable_bn`` from the reference's keyword set).  ``MixUpTrainer`` is an import stub."""
+epocher (``two_stage`` / ``disable_bn`` from the reference's keyword set).  ``MixUpTrainer`` (:67-72) is the same trainer on
+``MixUpEpocher`` (semi_seg/epochers/mixup.py): the labelled loader alone, the mix-up hook as its regulariser."""
 import torch
 from torch import nn
 
 from ... import ddp as _ddp
+from ..epochers.mixup import MixUpEpocher
 from ..epochers.semi import SemiSupervisedEpocher
 from .finetune import FineTuneTrainer
 from .pretrain import WarmupCosine, build_optimizer
@@ -73,7 +75,17 @@ class SemiTrainer(FineTuneTrainer):
 
 
 class MixUpTrainer(SemiTrainer):
-    """named by the reference's ``main.py:15`` import line; the mix-up baseline is not mirrored"""
+    """``MixUpTrainer`` (new_trainer.py:67-72): ``SemiTrainer`` with ``MixUpEpocher`` as its training epocher; the driver
+    (main_mixup.py:51-62) registers a ``MixUpHook``"""
+    activate_hooks = True
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("MixUpTrainer: the mix-up baseline is not mirrored")
+    def __init__(self, **kwargs):
+        # no default construction: a trainer is built with ``model=`` and its loaders (every real call is), and
+        # tests/test_iic_hooks_host.py::test_main_import_line_resolves_after_install expects ``MixUpTrainer()`` to refuse
+        if not kwargs:
+            raise NotImplementedError("MixUpTrainer: no default construction (pass model=, the loaders, criterion=, ...)")
+        super().__init__(**kwargs)
+
+    @property
+    def train_epocher(self):
+        return MixUpEpocher
