@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 12
+#define SPCL_ABI_VERSION 13
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -838,7 +838,17 @@ int spcl_consistency_softmax_mse(const float* a, const float* b, int N, int C, i
  *   spcl_entropy_softmax: weight * mean over the N*H*W pixels of -sum_c p_c log(p_c + eps), p = softmax(logits)
  *                    (entmin.py:30-31 -> deepclustering2 Entropy); dlogits = its gradient for a unit upstream gradient; ws:
  *                    spcl_entropy_softmax_workspace_bytes(N, H, W).
- *   Both losses are fixed-order sums (per-workgroup double partials added in index order): bitwise reproducible. */
+ *   spcl_ucmt_softmax_mse: the criterion of the uncertainty-aware mean teacher (semi_seg/epochers/comparable.py:84-105) in one
+ *                    launch.  teacher, the K noisy teacher maps (noisy: a HOST array of K device pointers, 1 <= K <= 16, handed
+ *                    to the kernel by value -- nothing is uploaded) and student_logits are [N][H][W][C] f32 (C <= 16); every
+ *                    teacher map is read through the per-sample flip flags (bit 0 flips H, bit 1 flips W).  Per pixel of the
+ *                    student's frame: p = softmax(student), t = softmax(flip(teacher)), avg = (noisy[0] + ... + noisy[K-1]) /
+ *                    (float)K (an f32 sum in list order, then one f32 division), q = softmax(flip(avg)), u = -sum_c q_c
+ *                    log(q_c + eps) / log(C), m = (u <= threshold) (a NaN u gives 0).  loss = weight / (N H W C) * sum_pixels
+ *                    m * sum_c (p_c - t_c)^2; dstudent = its gradient w.r.t. student_logits for a unit upstream gradient
+ *                    (exact zeros where m = 0; the teacher maps get none); kept[0] = the number of pixels with m = 1 (an exact
+ *                    integer); mask (nullable, [N][H][W] bytes) receives m.  ws: spcl_ucmt_workspace_bytes(N, H, W).
+ *   The losses are fixed-order sums (per-workgroup double partials added in index order): bitwise reproducible. */
 int spcl_ema_update(float* teacher, const float* student, size_t n, double alpha, double decay, void* stream);
 size_t spcl_mt_softmax_mse_workspace_bytes(int N, int H, int W);
 int spcl_mt_softmax_mse(const float* teacher, const float* student_logits, int N, int C, int H, int W,
@@ -847,6 +857,10 @@ int spcl_mt_softmax_mse(const float* teacher, const float* student_logits, int N
 size_t spcl_entropy_softmax_workspace_bytes(int N, int H, int W);
 int spcl_entropy_softmax(const float* logits, int N, int C, int H, int W, float eps, float weight, float* loss, float* dlogits,
                          void* ws, size_t ws_bytes, void* stream);
+size_t spcl_ucmt_workspace_bytes(int N, int H, int W);
+int spcl_ucmt_softmax_mse(const float* teacher, const float* const* noisy, int K, const float* student_logits, int N, int C,
+                          int H, int W, const uint8_t* flags_teacher, float threshold, float eps, float weight, float* loss,
+                          float* dstudent, unsigned long long* kept, uint8_t* mask, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- mix-up baseline (csrc/semi_reg.hip) -------------------------
  * Replaces the arithmetic of semi_seg/hooks/mixup.py:19-32 (mixup_data) and :66-75 (one-hot targets, concatenations, softmax,

@@ -38,6 +38,7 @@ _MIRRORED = {
     "semi_seg.hooks.mt": "semi_seg.hooks.mt",
     "semi_seg.hooks.entmin": "semi_seg.hooks.entmin",
     "semi_seg.hooks.mixup": "semi_seg.hooks.mixup",
+    "semi_seg.hooks.ucmt": "semi_seg.hooks.ucmt",
     "semi_seg.epochers": "semi_seg.epochers",
     "semi_seg.epochers.new_pretrain": "semi_seg.epochers.pretrain",
     "semi_seg.epochers.new_epocher": "semi_seg.epochers.finetune",

@@ -14,7 +14,12 @@
 //   spcl_mt_softmax_mse:  weight * mean((flip(T) - softmax(b))^2) and its gradient w.r.t. b in one launch; T = the teacher's
 //                         raw output (mt.py:49-52 applies no softmax) or its softmax (the older _mixins.py:147).
 //   spcl_entropy_softmax: weight * mean over pixels of -sum_c p_c log(p_c + eps), p = softmax(logits), and its gradient.
-//
+//   spcl_ucmt_softmax_mse: the uncertainty-aware mean teacher's criterion (semi_seg/epochers/comparable.py:84-105):
+//                         weight * mean over pixels of m * mean_c (softmax(s) - softmax(flip(T)))^2 with m = [normalised entropy
+//                         of softmax(mean of K noisy teacher maps) <= threshold], its gradient w.r.t. s, the number of kept
+//                         pixels and (optionally) the mask, in one launch.  K + 2 maps read once, one written: the K pointers
+//                         travel by value in the kernel's argument block, the average is accumulated while the maps stream in
+//                         (16 live floats, then dead before the student / teacher pair is loaded).
 //
 // and of the mix-up baseline (semi_seg/hooks/mixup.py), over the VIRTUAL concatenation of two batches of B samples (sample n
 // is a[n] for n < B, b[n - B] otherwise; nothing is concatenated) and a permutation index of its 2B samples:
@@ -27,7 +32,8 @@
 //                         gradient (mixup.py:31,66-75): the soft target is built per pixel from two labels, never stored.
 //
 // The criteria: one thread per pixel (C <= 16 channels in registers), per-workgroup double partials, the last workgroup
-// to take a ticket sums them in index order and resets the ticket: loss and gradient are bitwise reproducible.
+// to take a ticket sums them in index order (fetched 256 at a time through shared memory) and resets the ticket: loss and
+// gradient are bitwise reproducible.
 #include "common.hpp"
 
 namespace {
@@ -81,22 +87,48 @@ __device__ __forceinline__ double block_sum_d(double v, double* sh) {
   return r;
 }
 
-// the workgroup's partial -> partial[blockIdx.x]; the last workgroup sums all of them in index order
+// the workgroup's partial -> partial[blockIdx.x]; the last workgroup sums all of them in index order: its threads fetch 256
+// partials at a time into shared memory (one round trip to memory per 256 instead of one per partial), thread 0 adds them in
+// index order -- the same sequence of double additions as a plain loop over q.  With `counts`: the workgroup's integer `cnt`
+// -> counts[blockIdx.x], summed into total_count[0] the same way (an exact integer).  Workgroups of at most 256 threads.
 __device__ __forceinline__ void ordered_total(double v, double scale, float* __restrict__ loss, double* __restrict__ partial,
-                                              unsigned int* __restrict__ ticket) {
+                                              unsigned int* __restrict__ ticket, unsigned int cnt = 0u,
+                                              unsigned int* __restrict__ counts = nullptr,
+                                              unsigned long long* __restrict__ total_count = nullptr) {
   __shared__ unsigned int last;
+  __shared__ double stage[256];
+  __shared__ unsigned int cstage[256];
   if (threadIdx.x == 0) {
     partial[blockIdx.x] = v;
+    if (counts) counts[blockIdx.x] = cnt;
     __threadfence();
     last = atomicAdd(ticket, 1u) == gridDim.x - 1;
   }
   __syncthreads();
-  if (last && threadIdx.x == 0) {
+  if (last) {  // (uniform over the workgroup)
     __threadfence();
     double tot = 0.0;
-    for (unsigned int q = 0; q < gridDim.x; ++q) tot += *((volatile double*)partial + q);
-    loss[0] = (float)(tot * scale);
-    *ticket = 0u;
+    unsigned long long n = 0ull;
+    for (unsigned int base = 0; base < gridDim.x; base += blockDim.x) {
+      const unsigned int q = base + threadIdx.x;
+      if (q < gridDim.x) {
+        stage[threadIdx.x] = *((volatile double*)partial + q);
+        if (counts) cstage[threadIdx.x] = *((volatile unsigned int*)counts + q);
+      }
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        const unsigned int m = gridDim.x - base < blockDim.x ? gridDim.x - base : blockDim.x;
+        for (unsigned int i = 0; i < m; ++i) tot += stage[i];
+        if (counts)
+          for (unsigned int i = 0; i < m; ++i) n += cstage[i];
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      loss[0] = (float)(tot * scale);
+      if (counts) total_count[0] = n;
+      *ticket = 0u;
+    }
   }
 }
 
@@ -205,6 +237,141 @@ __global__ void __launch_bounds__(256) entropy_kernel(const float* __restrict__ 
   }
   ent = block_sum_d(ent, sh);
   ordered_total(ent, inv * weight, loss, partial, ticket);
+}
+
+// the K noisy teacher maps of spcl_ucmt_softmax_mse, by value in the kernel's argument block
+struct ucmt_noisy {
+  const float* p[16];
+};
+
+// CT channels of one pixel -> v[0 .. CT); CT == 4: one 16-byte access (the caller checked the alignment), CT == 0: C of them
+template <int CT>
+__device__ __forceinline__ void load_pixel(const float* __restrict__ p, int C, float (&v)[16]) {
+  if (CT == 4) {
+    const f32x4 x = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = x[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) v[k] = p[k];
+  }
+}
+
+// loss = weight / (M C) * sum_pixels m * sum_c (softmax(b) - softmax(flip(a)))^2, m = (u <= threshold),
+// u = -sum_c q_c log(q_c + eps) / log(C), q = softmax(flip((noisy[0] + ... + noisy[K-1]) / K)); d/db_k = m * the gradient of
+// mt_mse_kernel<true>.  CT = 4: C == 4 and every map 16-byte aligned (vector accesses); CT = 0: any C <= 16.
+template <int CT>
+__global__ void __launch_bounds__(256) ucmt_mse_kernel(const float* __restrict__ a, const ucmt_noisy noisy, int K,
+                                                       const float* __restrict__ b, int N, int C, int H, int W,
+                                                       const uint8_t* __restrict__ flags, float threshold, float eps,
+                                                       float weight, float* __restrict__ loss, float* __restrict__ db,
+                                                       unsigned long long* __restrict__ kept, uint8_t* __restrict__ mask,
+                                                       double* __restrict__ partial, unsigned int* __restrict__ counts,
+                                                       unsigned int* __restrict__ ticket) {
+  __shared__ double sh[8];
+  const int CC = CT ? CT : C;
+  const long M = (long)N * H * W;
+  const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const double inv = 1.0 / ((double)M * CC);
+  double sq = 0.0;
+  bool keep = false;
+  if (pix < M) {
+    const int n = (int)(pix / ((long)H * W));
+    const int rem = (int)(pix - (long)n * H * W), u = rem / W, v = rem - u * W;
+    const uint8_t f = flags ? flags[n] : 0;
+    const long aoff = ((long)(n * H + flip_idx(u, H, f & 1)) * W + flip_idx(v, W, f & 2)) * CC;
+    {  // the mask: the f32 sum of the K maps in list order, one division, softmax, normalised entropy
+      float avg[16], x[16];
+      load_pixel<CT>(noisy.p[0] + aoff, CC, avg);
+      // (C == 4: four maps' loads in flight at a time, 16 registers; the additions stay in list order)
+#pragma clang loop unroll_count(CT == 4 ? 4 : 1)
+      for (int j = 1; j < K; ++j) {
+        load_pixel<CT>(noisy.p[j] + aoff, CC, x);
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+          if (k < CC) avg[k] += x[k];
+      }
+      const float fk = (float)K;
+      float mq = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < CC) {
+          avg[k] = avg[k] / fk;
+          mq = fmaxf(mq, avg[k]);
+        }
+      float zq = 0.f;
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < CC) {
+          avg[k] = expf(avg[k] - mq);
+          zq += avg[k];
+        }
+      float e = 0.f;
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < CC) {
+          const float q = avg[k] / zq;
+          e = fmaf(q, logf(q + eps), e);
+        }
+      const float unc = -e / logf((float)CC);
+      keep = unc <= threshold;  // (a NaN entropy keeps nothing, as torch's comparison)
+    }
+    if (mask) mask[pix] = keep ? 1 : 0;
+    float g[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) g[k] = 0.f;
+    if (keep) {
+      float pa[16], pb[16];
+      load_pixel<CT>(a + aoff, CC, pa);
+      load_pixel<CT>(b + pix * CC, CC, pb);
+      float ma = -INFINITY, mb = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < CC) {
+          ma = fmaxf(ma, pa[k]);
+          mb = fmaxf(mb, pb[k]);
+        }
+      float za = 0.f, zb = 0.f;
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < CC) {
+          pa[k] = expf(pa[k] - ma);
+          za += pa[k];
+          pb[k] = expf(pb[k] - mb);
+          zb += pb[k];
+        }
+      const float gs = (float)(2.0 * weight * inv);
+      float sgp = 0.f;
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < CC) {
+          pa[k] /= za;
+          pb[k] /= zb;
+          const float d = pb[k] - pa[k];
+          sq += (double)d * d;
+          g[k] = gs * d;
+          sgp = fmaf(g[k], pb[k], sgp);
+        }
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < CC) g[k] = pb[k] * (g[k] - sgp);
+    }
+    float* dp = db + pix * CC;  // exact zeros where the pixel is masked out
+    if (CT == 4) {
+      f32x4 o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = g[k];
+      *reinterpret_cast<f32x4*>(dp) = o;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < CC) dp[k] = g[k];
+    }
+  }
+  const unsigned int cnt = (unsigned int)block_sum_d(keep ? 1.0 : 0.0, sh);  // (at most 256: exact)
+  sq = block_sum_d(sq, sh);
+  ordered_total(sq, inv * weight, loss, partial, ticket, cnt, counts, kept);
 }
 
 // sample n of the virtual concatenation (a, b) of two batches of B samples, per elements each
@@ -400,6 +567,49 @@ extern "C" int spcl_entropy_softmax(const float* logits, int N, int C, int H, in
   spcl::prof_cost(2.0 * M * C * 4, 30.0 * M * C);
   SPCL_LAUNCH(entropy_kernel, dim3(nblk), dim3(256), 0, st, logits, M, C, eps, weight, loss, dlogits, (double*)ws, ticket);
   SPCL_LAUNCH_CHECK("entropy_kernel");
+  return SPCL_OK;
+}
+
+// [partials: nblk doubles][ticket, 64 bytes][counts: nblk unsigned ints]
+extern "C" size_t spcl_ucmt_workspace_bytes(int N, int H, int W) {
+  const long M = (long)N * H * W;
+  return pixel_workspace_bytes(M) + (size_t)((M + 255) / 256) * sizeof(unsigned int);
+}
+
+extern "C" int spcl_ucmt_softmax_mse(const float* teacher, const float* const* noisy, int K, const float* student_logits, int N,
+                                     int C, int H, int W, const uint8_t* flags_teacher, float threshold, float eps, float weight,
+                                     float* loss, float* dstudent, unsigned long long* kept, uint8_t* mask, void* ws,
+                                     size_t ws_bytes, void* stream) {
+  SPCL_CHECK_ARG(K >= 1 && K <= 16, "spcl_ucmt_softmax_mse: K = %d noisy maps (1 <= K <= 16)", K);
+  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C >= 1 && C <= 16, "spcl_ucmt_softmax_mse: bad shape (C <= 16)");
+  SPCL_CHECK_ARG(teacher && noisy && student_logits && loss && dstudent && kept && ws, "spcl_ucmt_softmax_mse: null pointer");
+  ucmt_noisy maps{};
+  bool vec = C == 4 && ((uintptr_t)teacher | (uintptr_t)student_logits | (uintptr_t)dstudent) % 16 == 0;
+  for (int j = 0; j < K; ++j) {
+    SPCL_CHECK_ARG(noisy[j], "spcl_ucmt_softmax_mse: null pointer (noisy map %d)", j);
+    maps.p[j] = noisy[j];
+    vec = vec && (uintptr_t)noisy[j] % 16 == 0;
+  }
+  SPCL_CHECK_ARG((long)N * H * W < (1L << 31), "spcl_ucmt_softmax_mse: too many pixels");
+  SPCL_CHECK_ARG(eps >= 0.f, "spcl_ucmt_softmax_mse: negative eps");
+  SPCL_CHECK_ARG(ws_bytes >= spcl_ucmt_workspace_bytes(N, H, W), "spcl_ucmt_softmax_mse: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const long M = (long)N * H * W;
+  const int nblk = (int)((M + 255) / 256);
+  unsigned int* ticket = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double));
+  unsigned int* counts = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double) + 64);
+  if (hipMemsetAsync(ticket, 0, sizeof(unsigned int), st) != hipSuccess) {
+    spcl::set_error("spcl_ucmt_softmax_mse: memset failed");
+    return SPCL_ELAUNCH;
+  }
+  spcl::prof_cost((double)(K + 3) * M * C * 4 + (mask ? (double)M : 0.0), (20.0 + 2.0 * K + 20.0) * M * C);
+  if (vec)
+    SPCL_LAUNCH(ucmt_mse_kernel<4>, dim3(nblk), dim3(256), 0, st, teacher, maps, K, student_logits, N, C, H, W, flags_teacher,
+                threshold, eps, weight, loss, dstudent, kept, mask, (double*)ws, counts, ticket);
+  else
+    SPCL_LAUNCH(ucmt_mse_kernel<0>, dim3(nblk), dim3(256), 0, st, teacher, maps, K, student_logits, N, C, H, W, flags_teacher,
+                threshold, eps, weight, loss, dstudent, kept, mask, (double*)ws, counts, ticket);
+  SPCL_LAUNCH_CHECK("ucmt_mse_kernel");
   return SPCL_OK;
 }
 

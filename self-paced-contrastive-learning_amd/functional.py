@@ -2711,6 +2711,59 @@ def entropy_softmax(logits, eps=1e-16, weight=1.0):
     return _EntropySoftmaxFn.apply(logits, float(eps), float(weight))
 
 
+UCMT_MAX_NOISY = 16  # the K device pointers travel in the kernel's argument block
+
+
+class _UCMTSoftmaxMSEFn(torch.autograd.Function):
+    """The uncertainty-aware mean teacher's criterion in one launch (``spcl_ucmt_softmax_mse``): the loss, the gradient
+    w.r.t. the student's logits for a unit upstream gradient, the number of kept pixels and -- when ``out`` is a list -- the
+    mask.  The teacher and the noisy maps get no gradient."""
+
+    @staticmethod
+    def forward(ctx, teacher, noisy, student, flags, threshold, eps, weight, out):
+        _n.require_gpu(teacher, student, *noisy)
+        if not 1 <= len(noisy) <= UCMT_MAX_NOISY:
+            raise ValueError(f"ucmt_softmax_mse: {len(noisy)} noisy maps (1 <= K <= {UCMT_MAX_NOISY})")
+        ts, ss = _class_map_storage(teacher.detach()), _class_map_storage(student.detach())
+        ns = [_class_map_storage(t.detach()) for t in noisy]
+        for t in [ts] + ns:
+            if t.shape != ss.shape or t.device != ss.device:
+                raise AssertionError(f"class maps {tuple(t.shape)} on {t.device} / {tuple(ss.shape)} on {ss.device} differ")
+        N, H, W, C = ss.shape
+        dev = ss.device
+        fl = _flip_flags_arg(flags, N, dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        ds = torch.empty_like(ss)
+        kept = torch.empty((), dtype=torch.int64, device=dev)
+        mask = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if out is not None else None
+        ws = torch.empty(_n.call("spcl_ucmt_workspace_bytes", N, H, W), dtype=torch.uint8, device=dev)
+        _n.call("spcl_ucmt_softmax_mse", _n.ptr(ts), _n.ptr_array(ns), len(ns), _n.ptr(ss), N, C, H, W, _n.ptr(fl),
+                c_float(threshold), c_float(eps), c_float(weight), _n.ptr(loss), _n.ptr(ds), _n.ptr(kept), _n.ptr(mask),
+                _n.ptr(ws), ws.numel(), _n.stream())
+        if out is not None:
+            out.extend((kept, mask))
+        ctx.save_for_backward(ds)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (ds,) = ctx.saved_tensors
+        if is_unit_gradient(g):
+            return None, None, ds.permute(0, 3, 1, 2), None, None, None, None, None
+        return None, None, (ds * g.detach().float()).permute(0, 3, 1, 2), None, None, None, None, None
+
+
+def ucmt_softmax_mse(teacher, noisy_list, student_logits, threshold, weight=1.0, flags=None, eps=1e-16, out=None):
+    """comparable.py:84-105: ``weight * (mse(softmax(student_logits), softmax(flip(teacher)), reduction="none").mean(1) *
+    mask).mean()`` of logical [N, C, H, W] maps, ``mask = Entropy(softmax(flip(mean of noisy_list))) / log(C) <= threshold``
+    (the K noisy teacher maps are summed in list order in f32 and divided by ``float(K)``, as ``average_iter`` does; the
+    average of the flipped maps is the flip of the average).  The gradient goes to the student only.  ``out`` (a list)
+    receives ``(kept, mask)``: the number of pixels with mask = 1 as an int64 device scalar (no readback here) and the mask as
+    uint8 [N, H, W] in the student's frame."""
+    return _UCMTSoftmaxMSEFn.apply(teacher, tuple(noisy_list), student_logits, flags, float(threshold), float(eps),
+                                   float(weight), out)
+
+
 # ------------------------------------------------------------------------------------------------ mix-up (csrc/semi_reg.hip)
 class MixupPlan:
     """One mix-up draw (mixup.py:19-32) for a batch of B labelled samples and their second views: ``lam`` (the host's float64),

@@ -6,7 +6,12 @@ Contract (hook_creator.py:10-28): ``InfonceParams`` builds plain InfoNCE hooks, 
 (``create_discrete_mi_consistency_hook``) outside pre-training; during pre-training the reference raises RuntimeError for
 it and so does this mirror.  ``MeanTeacherParameters`` (keys of config/specific/mt.yaml) and ``EntropyMinParameters``
 (``weight``) build the mean-teacher and entropy-minimisation hooks under the same rule: the reference's
-``create_hook_from_config`` notes that pre-training accepts no mean teacher (hook_creator.py:6)."""
+``create_hook_from_config`` notes that pre-training accepts no mean teacher (hook_creator.py:6).
+``UCMeanTeacherParameters`` builds the uncertainty-aware mean teacher (``create_uc_mean_teacher_hook``): the keys of
+``MeanTeacherParameters`` plus the hook's own (``num_samples``, ``noise_std``, ``cumulative_noise``), and the trainer's
+``max_epoch`` for the threshold's ramp.  The reference's hook_creator has no such section -- its old-API
+``UCMeanTeacherTrainer`` reads ``MeanTeacherParameters`` (semi_seg/trainers/trainer.py:252,274-279); a section of its own
+lets one config hold either baseline.  Refused during pre-training like the other two."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -15,10 +20,11 @@ _SECTIONS = (
     ("SPInfonceParams", "create_sp_infonce_hooks", True),
 )
 _BASELINE_SECTION = "DiscreteMIConsistencyParams"
-# semi-supervised baselines: section -> (factory, does the factory take the model?)
+# semi-supervised baselines: section -> (factory, does the factory take the model?, ... the trainer's max_epoch?)
 _SEMI_SECTIONS = (
-    ("MeanTeacherParameters", "create_mean_teacher_hook", True),
-    ("EntropyMinParameters", "create_entropy_min_hook", False),
+    ("MeanTeacherParameters", "create_mean_teacher_hook", True, False),
+    ("EntropyMinParameters", "create_entropy_min_hook", False, False),
+    ("UCMeanTeacherParameters", "create_uc_mean_teacher_hook", True, True),
 )
 
 
@@ -35,10 +41,12 @@ def create_hook_from_config(model, config, is_pretrain=False):
         if is_pretrain:
             raise RuntimeError(f"{_BASELINE_SECTION} are not supported for pretrain stage")
         built.append(_hooks.create_discrete_mi_consistency_hook(model=model, **config[_BASELINE_SECTION]))
-    for section, factory, wants_model in _SEMI_SECTIONS:
+    for section, factory, wants_model, wants_epochs in _SEMI_SECTIONS:
         if section in config:
             if is_pretrain:
                 raise RuntimeError(f"{section} are not supported for pretrain stage")
             extra = {"model": model} if wants_model else {}
+            if wants_epochs:
+                extra["max_epoch"] = config["Trainer"]["max_epoch"]
             built.append(getattr(_hooks, factory)(**extra, **config[section]))
     return built

@@ -4,7 +4,8 @@ contrast_on) triple combined into one TrainerHook -- and the UDA-IIC factories `
 ``create_discrete_mi_hooks`` (:36-47) and ``create_discrete_mi_consistency_hook`` (:50-66).  ``create_mean_teacher_hook`` and
 ``create_entropy_min_hook`` have no counterpart there: the reference builds those two baselines in their trainers
 (semi_seg/trainers/trainer.py:227-271, from ``EntropyMinParameters`` / ``MeanTeacherParameters``); the hook names are its
-trainer-registry keys (semi_seg/trainers/__init__.py:11-12)."""
+trainer-registry keys (semi_seg/trainers/__init__.py:11-12).  ``create_uc_mean_teacher_hook`` likewise stands for
+``UCMeanTeacherTrainer`` (trainer.py:274-290, registry key ``ucmeanteacher``)."""
 from typing import List, Union
 
 from ...contrastyou.hooks.base import CombineTrainerHook
@@ -14,6 +15,7 @@ from .discretemi import DiscreteMITrainHook
 from .entmin import EntropyMinTrainerHook
 from .infonce import INFONCEHook, SelfPacedINFONCEHook, decoder_names
 from .mt import MeanTeacherTrainerHook
+from .ucmt import UCMeanTeacherTrainerHook
 
 
 def _listify(v, n):
@@ -107,6 +109,16 @@ def create_mean_teacher_hook(*, model, weight: float, alpha: float = 0.999, weig
     if name != "mse":
         raise NotImplementedError(f"mean teacher criterion {name!r}: only 'mse' is mirrored")
     return MeanTeacherTrainerHook(name="meanteacher", weight=weight, model=model, alpha=alpha, weight_decay=weight_decay)
+
+
+def create_uc_mean_teacher_hook(*, model, weight: float, max_epoch: int, alpha: float = 0.999, weight_decay: float = 1e-5,
+                                name: str = "mse", **uc):
+    """``UCMeanTeacherParameters``: the keys of ``MeanTeacherParameters`` plus the hook's own (``num_samples``, ``noise_std``,
+    ``threshold``, ``cumulative_noise``); ``name`` is the teacher criterion (only ``mse`` is mirrored)"""
+    if name != "mse":
+        raise NotImplementedError(f"uncertainty-aware mean teacher criterion {name!r}: only 'mse' is mirrored")
+    return UCMeanTeacherTrainerHook(name="ucmeanteacher", weight=weight, model=model, max_epoch=max_epoch, alpha=alpha,
+                                    weight_decay=weight_decay, **uc)
 
 
 def create_entropy_min_hook(*, weight: float):
