@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 13
+#define SPCL_ABI_VERSION 14
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -821,6 +821,31 @@ int spcl_iic_joint_backward(const float* lx, const float* ly, long ld, int N, in
 size_t spcl_consistency_workspace_bytes(int N, int H, int W);
 int spcl_consistency_softmax_mse(const float* a, const float* b, int N, int C, int H, int W, const uint8_t* flags_a,
                                  float weight, float* loss, float* db, void* ws, size_t ws_bytes, void* stream);
+
+/* Patch-wise IIC segmentation criterion of the MIDL baseline (csrc/iic_patch.hip).  Replaces IIDSegmentationSmallPathLoss and
+ * patch_generator (contrastyou/losses/iic_loss.py:103-128, :154-162) as semi_seg/epochers/comparable.py:222 calls them on the
+ * segmentation output: there one F.conv2d and about twenty tensor ops per patch.
+ * lx / ly: class logits [N][H][W][C] f32 (2 <= C <= 16); PX = softmax(lx), PY = softmax(flip(ly)), flags_y: uint8 [N] (bit 0
+ * flips H, bit 1 flips W) applied to Y by indexing, or NULL.  0 <= pad <= 7, patch >= 2.  The patch starts along an axis of
+ * length h are 0, s, 2s, ... < h - patch and then max(h - patch, 0), s = patch / 2; the nP patches are all (row start, column
+ * start) pairs in row-major order, each clipped to the map.  Per patch P
+ *   J_P[dy][dx][i][j] = sum_{n, (u,v) in P} PX[n,i,u+dy-pad,v+dx-pad] PY[n,j,u,v]   (PX = 0 outside the PATCH)
+ * and loss_P = IIDSegmentationLoss of that joint (iic_loss.py:77-97: min-shift over the whole joint, per-displacement
+ * normalisation, symmetrisation, marginals, eps 1e-16, / T^2; lamda = 1), in float64 from 32.32 fixed-point joints.
+ *   spcl_iic_patch_plan:     argument check without a launch; gives the patch count, the workspace size in bytes and the
+ *                    number of f32 elements of dj (each output pointer may be NULL).
+ *   spcl_iic_patch_forward:  loss[0] = scale * mean_P loss_P; patch_loss (nullable, [nP]) = the loss_P themselves (not scaled);
+ *                    nan_flag[0] = 1 when any loss_P is NaN (iic_loss.py:123), else 0; dj = d loss / d J_P of every patch, in
+ *                    the layout spcl_iic_patch_backward reads.  ws is zeroed by the call.  Bitwise deterministic.
+ *   spcl_iic_patch_backward: dlx = d loss / d lx (times *gscale when non-NULL); dly, when non-NULL, the same for ly, written
+ *                    at Y's unflipped position.  A pixel gathers from every patch that covers it: each element is written
+ *                    exactly once, no atomics. */
+int spcl_iic_patch_plan(int N, int C, int H, int W, int pad, int patch, int* num_patches, size_t* ws_bytes, size_t* dj_elems);
+int spcl_iic_patch_forward(const float* lx, const float* ly, int N, int C, int H, int W, int pad, int patch,
+                           const uint8_t* flags_y, float scale, float* loss, float* patch_loss, int* nan_flag, float* dj,
+                           void* ws, size_t ws_bytes, void* stream);
+int spcl_iic_patch_backward(const float* lx, const float* ly, int N, int C, int H, int W, int pad, int patch,
+                            const uint8_t* flags_y, const float* dj, const float* gscale, float* dlx, float* dly, void* stream);
 
 /* ---------------------------------------------------------------- mean teacher / entropy minimisation (csrc/semi_reg.hip) ----
  * Replaces the arithmetic of semi_seg/hooks/mt.py:48-54 and semi_seg/hooks/entmin.py:30-34 of the reference.

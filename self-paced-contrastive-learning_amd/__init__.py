@@ -39,6 +39,7 @@ _MIRRORED = {
     "semi_seg.hooks.entmin": "semi_seg.hooks.entmin",
     "semi_seg.hooks.mixup": "semi_seg.hooks.mixup",
     "semi_seg.hooks.ucmt": "semi_seg.hooks.ucmt",
+    "semi_seg.hooks.midl": "semi_seg.hooks.midl",
     "semi_seg.epochers": "semi_seg.epochers",
     "semi_seg.epochers.new_pretrain": "semi_seg.epochers.pretrain",
     "semi_seg.epochers.new_epocher": "semi_seg.epochers.finetune",

@@ -1,6 +1,7 @@
-"""HIP-backed mirror of ``contrastyou/losses/iic_loss.py``: ``IIDLoss`` (:17-51), ``IIDSegmentationLoss`` (:54-100) and
-``compute_joint`` (:131-151), same call signatures.  The joint, the criterion and its gradient are csrc/iic.hip
-(functional.iic_loss); the hooks hand the cluster heads' LOGITS to it (the grouped softmax is applied as they are read).
+"""HIP-backed mirror of ``contrastyou/losses/iic_loss.py``: ``IIDLoss`` (:17-51), ``IIDSegmentationLoss`` (:54-100),
+``IIDSegmentationSmallPathLoss`` (:103-128), ``compute_joint`` (:131-151) and ``patch_generator`` (:154-162), same call
+signatures.  The joint, the criterion and its gradient are csrc/iic.hip (functional.iic_loss) and, patch-wise, csrc/iic_patch.hip
+(functional.iic_patch_loss); the hooks hand LOGITS to them (the softmax is applied as they are read).
 
 The reference's ``simplex`` asserts are host synchronisations; its UDA-IIC jobs run with PYTHONOPTIMIZE=1
 (script/script_generator_discreteMI.py:92), where they are compiled out.  The mirror leaves them out of the hot path:
@@ -121,9 +122,68 @@ class IIDSegmentationLoss(nn.Module):
             self._nan.flush()
 
 
+class IIDSegmentationSmallPathLoss(IIDSegmentationLoss):
+    """__call__(x_out [n, k, h, w], x_tf_out, mask=None) -> the mean of ``IIDSegmentationLoss`` over the overlapping
+    ``patch_size`` patches of the two maps (stride ``patch_size // 2``, the last patch pushed back to the border), all patches
+    in one pass of csrc/iic_patch.hip.  The NaN ``RuntimeError`` of iic_loss.py:123 carries the loss (not the list of patch
+    losses)."""
+
+    def __init__(self, lamda=1.0, padding=7, eps: float = sys.float_info.epsilon, patch_size=32, check_inputs: bool = False,
+                 lagged: bool = True) -> None:
+        if float(lamda) != 1.0:
+            raise NotImplementedError("IIDSegmentationSmallPathLoss: lamda != 1 (the MIDL baseline uses the default)")
+        super().__init__(lamda, padding, eps, check_inputs=check_inputs, lagged=lagged)
+        if isinstance(patch_size, (tuple, list)):
+            if len(set(patch_size)) != 1:
+                raise NotImplementedError(f"IIDSegmentationSmallPathLoss: square patches only, got {patch_size}")
+            patch_size = patch_size[0]
+        F_hip.iic_patch_starts(1, patch_size)  # (refuses patch_size < 2)
+        self._patch_size = (int(patch_size), int(patch_size))
+        self._step_size = (int(patch_size) // 2, int(patch_size) // 2)
+
+    def __call__(self, x_out: Tensor, x_tf_out: Tensor, mask: Tensor = None) -> Tensor:
+        assert x_out.shape == x_tf_out.shape, (x_out.shape, x_tf_out.shape)
+        if mask is not None:
+            raise NotImplementedError("IIDSegmentationSmallPathLoss: masks (not used by the MIDL baseline)")
+        if self.check_inputs:
+            assert _simplex(x_out)
+        return self.from_logits(_as_logits(x_out), _as_logits(x_tf_out))
+
+    def from_logits(self, lx: Tensor, ly: Tensor, *, num_subheads: int = 1, num_clusters: int = None, scale: float = 1.0,
+                    flags: Tensor = None) -> Tensor:
+        """``scale * self(softmax(lx), softmax(flip(ly)))`` of [n, k, h, w] logits (the hook's entry).  ``num_subheads`` /
+        ``num_clusters`` are the base class's keywords: one subhead of all k channels is the only layout here.  NOTE the
+        flags flip Y here (the MIDL epocher flips the detached map), where the base class's flip X."""
+        if int(num_subheads) != 1 or (num_clusters is not None and int(num_clusters) != lx.shape[1]):
+            raise NotImplementedError("IIDSegmentationSmallPathLoss: one subhead over all channels only")
+        out = []
+        loss = F_hip.iic_patch_loss(lx, ly, padding=self.padding, patch_size=self._patch_size[0], scale=scale, flags=flags,
+                                    out=out)
+        if self._nan is not None:
+            self._nan.push(out[1], loss)
+        elif int(out[1][0]):
+            raise RuntimeError(loss)
+        return loss
+
+    def __repr__(self):
+        return f"{self.__class__.__name__} with patch_size={self._patch_size} and padding={self.padding}."
+
+
 def compute_joint(x_out: Tensor, x_tf_out: Tensor, symmetric=True) -> Tensor:
     """iic_loss.py:131-151 (a small [n, k] product: plain tensor ops)"""
     p_i_j = (x_out.unsqueeze(2) * x_tf_out.unsqueeze(1)).sum(dim=0)
     if symmetric:
         p_i_j = (p_i_j + p_i_j.t()) / 2.0
     return p_i_j / p_i_j.sum()
+
+
+def patch_generator(feature_map, patch_size=(32, 32), step_size=(16, 16)):
+    """the crops ``IIDSegmentationSmallPathLoss`` averages over, in row-major order of their starts, for callers that import
+    the generator (the criterion above does not go through it).  The starts are ``functional.iic_patch_starts``; a
+    ``step_size`` other than half the patch is not what that rule describes and is refused."""
+    height, width = feature_map.shape[-2:]
+    if tuple(step_size) != (patch_size[0] // 2, patch_size[1] // 2):
+        raise NotImplementedError(f"patch_generator: step_size {tuple(step_size)} is not half of patch_size {tuple(patch_size)}")
+    for top in F_hip.iic_patch_starts(height, patch_size[0]):
+        for left in F_hip.iic_patch_starts(width, patch_size[1]):
+            yield feature_map[..., top:top + patch_size[0], left:left + patch_size[1]]

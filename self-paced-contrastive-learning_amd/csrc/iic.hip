@@ -25,43 +25,13 @@
 // PY[u-dy+p, v-dx+p, j]: dJ is uniform across the workgroup (scalar loads), the probabilities come from LDS, then the
 // grouped-softmax backward writes d(logits) (X's at its flipped position).  Each output is written once: deterministic.
 #include "common.hpp"
+#include "iic_common.hpp"
 
 namespace {
 
 constexpr int kFwdThreads = 256;
 constexpr int kFwdCW = 128;     // pixel columns staged per pass
 constexpr int kMaxItems = 4;    // (dx, 4x4 tile) items per thread
-constexpr double kFix = 4294967296.0;  // 2^32
-
-__device__ __forceinline__ int flip_idx(int x, int n, bool f) { return f ? n - 1 - x : x; }
-
-// softmax of subhead s of the logits row at (n, u, v) into dst[KP] (pad entries 0); zeros when out of the image
-template <int KP>
-__device__ __forceinline__ void stage_prob(const float* __restrict__ l, long ld, int H, int W, int n, int u, int v, int s,
-                                           int K, float* dst) {
-  if (u < 0 || u >= H || v < 0 || v >= W) {
-#pragma unroll
-    for (int k = 0; k < KP; ++k) dst[k] = 0.f;
-    return;
-  }
-  const float* p = l + ((long)(n * H + u) * W + v) * ld + (long)s * K;
-  float x[KP];
-  float m = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < KP; ++k) {
-    x[k] = k < K ? p[k] : -INFINITY;
-    m = fmaxf(m, x[k]);
-  }
-  float z = 0.f;
-#pragma unroll
-  for (int k = 0; k < KP; ++k) {
-    x[k] = k < K ? expf(x[k] - m) : 0.f;
-    z += x[k];
-  }
-  const float r = 1.f / z;
-#pragma unroll
-  for (int k = 0; k < KP; ++k) dst[k] = x[k] * r;
-}
 
 // grid (nband, T, S); rows r = n*H + u of Y, band b covers [b*R, min((b+1)*R, N*H))
 template <int KP>
@@ -249,25 +219,6 @@ __global__ void __launch_bounds__(256) iic_joint_bwd_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------------------- loss
 // grid (T*T, S), 256 threads: one displacement of one subhead each; the subhead's min is recomputed by each workgroup
 // (T^2 K^2 reads from L2).  The partial losses are summed in a fixed order by the last workgroup to finish.
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-  return t;
-}
-__device__ __forceinline__ double block_min_d(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = sh[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t = fmin(t, sh[w]);
-  return t;
-}
-
 __device__ __forceinline__ double jval(const long long* jacc, const float* jf, long e) {
   return jacc ? (double)jacc[e] / kFix : (double)jf[e];
 }

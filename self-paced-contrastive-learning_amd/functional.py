@@ -2594,6 +2594,70 @@ def iic_loss_from_joint(j, *, dense=True, scale=1.0):
     return loss, dj, flag
 
 
+def iic_patch_starts(h: int, patch_size: int):
+    """patch_generator's starts along an axis of length ``h`` (iic_loss.py:156-159): ``0, s, 2s, ... < h - patch_size`` and
+    then ``max(h - patch_size, 0)``, ``s = patch_size // 2``.  The one place the lists are computed on the Python side; the
+    library derives the same lists from (h, patch_size) and ``_IICPatchLossFn`` compares the counts."""
+    h, patch_size = int(h), int(patch_size)
+    if patch_size < 2:
+        raise ValueError(f"patch_size = {patch_size}: at least 2 (the stride is patch_size // 2)")
+    if h < 1:
+        raise ValueError(f"axis length {h}")
+    return list(range(0, h - patch_size, patch_size // 2)) + [max(h - patch_size, 0)]
+
+
+class _IICPatchLossFn(torch.autograd.Function):
+    """``scale * mean over patches of IIDSegmentationLoss(softmax(lx), softmax(flip(ly)))`` (IIDSegmentationSmallPathLoss) in
+    two launches -- every patch's joint, then every patch's criterion with dJ -- and one more in backward, in which a pixel
+    gathers from the patches that cover it.  ``lx`` / ``ly``: logical [N, C, H, W] f32 class logits.  Returns the loss;
+    ``out`` receives (per-patch losses f32 [nP], nan flag int32 [1])."""
+
+    @staticmethod
+    def forward(ctx, lx, ly, flags, pad, patch, scale, out):
+        _n.require_gpu(lx, ly)
+        xs, ys = _class_map_storage(lx.detach()), _class_map_storage(ly.detach())
+        if xs.shape != ys.shape:
+            raise AssertionError(f"class maps {tuple(xs.shape)} / {tuple(ys.shape)} differ")
+        N, H, W, C = xs.shape
+        dev = xs.device
+        n_patches, ws_bytes, dj_elems = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _n.call("spcl_iic_patch_plan", N, C, H, W, pad, patch, ctypes.byref(n_patches), ctypes.byref(ws_bytes),
+                ctypes.byref(dj_elems))
+        nP = len(iic_patch_starts(H, patch)) * len(iic_patch_starts(W, patch))
+        assert nP == n_patches.value, (nP, n_patches.value)
+        fl = _flip_flags_arg(flags, N, dev)
+        ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device=dev)
+        dj = torch.empty(dj_elems.value, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        per_patch = torch.empty(nP, dtype=torch.float32, device=dev)
+        flag = torch.empty(1, dtype=torch.int32, device=dev)
+        _n.call("spcl_iic_patch_forward", _n.ptr(xs), _n.ptr(ys), N, C, H, W, pad, patch, _n.ptr(fl), c_float(scale),
+                _n.ptr(loss), _n.ptr(per_patch), _n.ptr(flag), _n.ptr(dj), _n.ptr(ws), ws.numel(), _n.stream())
+        out.extend([per_patch, flag])
+        ctx.save_for_backward(xs, ys, dj, fl)
+        ctx.meta = (pad, patch)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        xs, ys, dj, fl = ctx.saved_tensors
+        pad, patch = ctx.meta
+        N, H, W, C = xs.shape
+        gs = None if is_unit_gradient(g) else g.detach().float().reshape(1).contiguous()
+        dlx = torch.empty_like(xs)
+        dly = torch.empty_like(ys) if ctx.needs_input_grad[1] else None
+        _n.call("spcl_iic_patch_backward", _n.ptr(xs), _n.ptr(ys), N, C, H, W, pad, patch, _n.ptr(fl), _n.ptr(dj), _n.ptr(gs),
+                _n.ptr(dlx), _n.ptr(dly), _n.stream())
+        return dlx.permute(0, 3, 1, 2), None if dly is None else dly.permute(0, 3, 1, 2), None, None, None, None, None
+
+
+def iic_patch_loss(lx, ly, *, padding, patch_size, scale=1.0, flags=None, out=None):
+    """``scale * IIDSegmentationSmallPathLoss(padding, patch_size)(softmax(lx), softmax(flip(ly)))`` of logical [N, C, H, W]
+    logits (iic_loss.py:103-128); differentiable w.r.t. ``lx``, and w.r.t. ``ly`` when it requires grad.  ``flags`` flip Y.
+    ``out`` (a list) receives (per-patch losses [nP], not scaled; nan flag int32 [1])."""
+    return _IICPatchLossFn.apply(lx, ly, flags, int(padding), int(patch_size), float(scale), [] if out is None else out)
+
+
 class _ConsistencyFn(torch.autograd.Function):
     """``weight * MSELoss(softmax(flip(a)).detach(), softmax(b))`` in one launch; the gradient w.r.t. ``b`` for a unit upstream
     gradient is written by the same launch (``a`` gets none: the reference detaches it)."""

@@ -11,7 +11,11 @@ it and so does this mirror.  ``MeanTeacherParameters`` (keys of config/specific/
 ``MeanTeacherParameters`` plus the hook's own (``num_samples``, ``noise_std``, ``cumulative_noise``), and the trainer's
 ``max_epoch`` for the threshold's ramp.  The reference's hook_creator has no such section -- its old-API
 ``UCMeanTeacherTrainer`` reads ``MeanTeacherParameters`` (semi_seg/trainers/trainer.py:252,274-279); a section of its own
-lets one config hold either baseline.  Refused during pre-training like the other two."""
+lets one config hold either baseline.  Refused during pre-training like the other two.
+``MIDLPaperParameters`` builds the MIDL baseline (``create_midl_hook``: the consistency hook plus the patch-wise IIC
+segmentation criterion): the keys of config/specific/midl.yaml (``iic_weight``, ``padding``, ``patch_size``) plus
+``consistency_weight`` and ``name``, which the reference's old-API ``MIDLTrainer`` reads from ``UDARegCriterion``
+(semi_seg/trainers/trainer.py:24-26,42) -- a section of its own for the same reason.  Refused during pre-training too."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -25,6 +29,7 @@ _SEMI_SECTIONS = (
     ("MeanTeacherParameters", "create_mean_teacher_hook", True, False),
     ("EntropyMinParameters", "create_entropy_min_hook", False, False),
     ("UCMeanTeacherParameters", "create_uc_mean_teacher_hook", True, True),
+    ("MIDLPaperParameters", "create_midl_hook", False, False),
 )
 
 

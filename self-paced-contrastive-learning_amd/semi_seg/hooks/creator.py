@@ -5,7 +5,8 @@ contrast_on) triple combined into one TrainerHook -- and the UDA-IIC factories `
 ``create_entropy_min_hook`` have no counterpart there: the reference builds those two baselines in their trainers
 (semi_seg/trainers/trainer.py:227-271, from ``EntropyMinParameters`` / ``MeanTeacherParameters``); the hook names are its
 trainer-registry keys (semi_seg/trainers/__init__.py:11-12).  ``create_uc_mean_teacher_hook`` likewise stands for
-``UCMeanTeacherTrainer`` (trainer.py:274-290, registry key ``ucmeanteacher``)."""
+``UCMeanTeacherTrainer`` (trainer.py:274-290, registry key ``ucmeanteacher``) and ``create_midl_hook`` for ``MIDLTrainer``
+(trainer.py:39-60, registry key ``midl``)."""
 from typing import List, Union
 
 from ...contrastyou.hooks.base import CombineTrainerHook
@@ -14,6 +15,7 @@ from .consistency import ConsistencyTrainerHook
 from .discretemi import DiscreteMITrainHook
 from .entmin import EntropyMinTrainerHook
 from .infonce import INFONCEHook, SelfPacedINFONCEHook, decoder_names
+from .midl import MIDLPaperTrainerHook
 from .mt import MeanTeacherTrainerHook
 from .ucmt import UCMeanTeacherTrainerHook
 
@@ -123,3 +125,15 @@ def create_uc_mean_teacher_hook(*, model, weight: float, max_epoch: int, alpha: 
 
 def create_entropy_min_hook(*, weight: float):
     return EntropyMinTrainerHook(name="entropy", weight=weight)
+
+
+def create_midl_hook(*, consistency_weight: float, iic_weight: float = 0.1, padding: int = 1, patch_size: int = 1024,
+                     name: str = "mse"):
+    """``MIDLPaperParameters``: the keys of config/specific/midl.yaml plus ``consistency_weight`` and ``name``, which the
+    reference's ``MIDLTrainer`` reads from ``UDARegCriterion`` (``weight`` and ``name``: trainer.py:24-26,42); ``name`` is the
+    consistency criterion (only ``mse`` is mirrored).  The sum is comparable.py:224: ``uda_loss * consistency_weight +
+    iic_loss * iic_weight``."""
+    if name != "mse":
+        raise NotImplementedError(f"MIDL consistency criterion {name!r}: only 'mse' is mirrored")
+    return CombineTrainerHook(ConsistencyTrainerHook(name="consistency", weight=consistency_weight),
+                              MIDLPaperTrainerHook(name="midl", weight=iic_weight, padding=padding, patch_size=patch_size))
