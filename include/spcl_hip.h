@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 14
+#define SPCL_ABI_VERSION 15
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -912,6 +912,67 @@ size_t spcl_mixup_kl_workspace_bytes(int N2, int H, int W);
 int spcl_mixup_kl_onehot(const float* logits, const int64_t* target, const int64_t* target_tf, const int* index, int N2, int C,
                          int H, int W, float lam, float oml, float eps, float weight, float* loss, float* dlogits, void* ws,
                          size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- adversarial baseline: DCGAN discriminator (csrc/discr.hip) ---
+ * Replaces the ATen sequence of semi_seg/arch/discr.py:17-36 (Conv2d(., ., 4, 2, 1, bias=False) / BatchNorm2d / LeakyReLU(0.2)
+ * x 4, Conv2d(., 1, 4, 1, 0) / Sigmoid) and the nn.BCELoss of semi_seg/epochers/new_comparable.py:124,162-163,183-191 (ABI 15).
+ * All f32; every sum has a fixed order (no floating-point atomics): bitwise reproducible.
+ *
+ * Lowering: a 4x4 stride-2 padding-1 convolution is a rows product (spcl_rows_linear_*) over PATCH ROWS
+ *   rows[m][k],  m = (n Ho + oh) Wo + ow,  k = 16 c + 4 kh + kw,  Ho = (H + 2 - 4) / 2 + 1 (floor), Wo likewise,
+ *   rows[m][k] = T(x[n][c][2 oh - 1 + kh][2 ow - 1 + kw]) inside the image and exactly 0 at a padded tap (NOT T(0)).
+ * In this k order the contiguous [Cout][C][4][4] parameter IS the weight matrix Wr[Cout][16 C] of the product, and its gradient
+ * dWr the parameter's gradient: nothing is repacked or permuted, in either direction, ever.  The layer's output y[M][Cout] =
+ * rows Wr^T is the NHWC map the next layer reads.
+ * T (mode): 0 identity | 1 LeakyReLU(0.2)(x), x a stored pre-activation | 2 LeakyReLU(0.2)(scale[c] x + shift[c]), x a stored
+ * pre-BatchNorm map.  (The slope is 0.2: the leaky_in flags of the rows product are 0.01 and are not used here.)
+ *
+ *   spcl_patch4s2_rows_forward: the input is the channel concatenation of two strided f32 maps, a (Ca channels, element
+ *                    strides a_sn/a_sc/a_sh/a_sw) in front of b (Cb channels; b NULL with Cb = 0): a class map, or image + class
+ *                    map, read where it lies, NCHW or channels-last.  C = Ca + Cb; rows [N Ho Wo][16 C].  A dense NHWC input with
+ *                    C % 4 == 0 (an inner layer) is read in 16-byte pieces along c and written in 16-byte pieces along kw.
+ *   spcl_patch4s2_rows_backward: gather form -- every input pixel sums the <= 2 x 2 output positions / taps that cover it from
+ *                    drows [N Ho Wo][16 C] in a fixed order and multiplies by T'; in mode 2 the result is the gradient w.r.t.
+ *                    the BatchNorm OUTPUT scale x + shift (spcl_rows_bn_backward finishes it).  x [N][H][W][C] is the stored map
+ *                    of modes 1, 2 (NULL in mode 0).  dx [N][H][W][C - c_lo] dense NHWC holds channels c_lo .. C-1 (c_lo > 0, mode
+ *                    0 only: the image channels in front of a class map get no gradient).
+ *   spcl_rows_bn_forward: training-mode BatchNorm statistics of x [M][C] (C % 4 == 0, C <= 1024, M >= 2) in ONE launch: sums of
+ *                    (x - x[0][c]) and its square per slab of rows, folded in slab order in double by the workgroup that finishes
+ *                    last.  stats [4][C] = mean, 1 / sqrt(var + eps) (biased var), scale = gamma invstd, shift = beta - mean
+ *                    scale (what mode 2 reads).  running_mean / running_var (both or neither) are updated with `momentum` and the
+ *                    unbiased variance; num_batches_tracked is the caller's.  ws: spcl_rows_bn_workspace_bytes(M, C).
+ *   spcl_rows_bn_eval_affine: stats [4][C] from the running statistics (eval mode).
+ *   spcl_rows_bn_backward: from du = dLoss/d(scale x + shift): dbeta = sum du, dgamma = sum du xhat (one launch, folded as
+ *                    above), dx = gamma invstd (du - dbeta / M - xhat dgamma / M) (second launch); with training = 0 the batch
+ *                    terms are left out (dx = scale du).  dx may alias du.
+ *   spcl_discr_head_forward: Conv2d(C, 1, 4, 1, 0) over LeakyReLU(0.2)(scale x + shift) of x [N][H][W][C] (C % 4 == 0, H, W >= 4),
+ *                    w [16 C] in the k order above (the [1][C][4][4] parameter): t [M] logits (M = N (H-3) (W-3)), d [M] = sigmoid(t); with y = 0 or 1 also
+ *                    loss[0] = mean BCE(d, y) and dt [M] = (d - y) / M (d - 1 formed as -sigmoid(-t), no cancellation), with y < 0 neither (loss, dt may be NULL).  One launch, the
+ *                    mean folded in index order in double by the last workgroup.  The loss is evaluated as softplus(-t) (y = 1) /
+ *                    softplus(t) (y = 0), softplus(z) = max(z, 0) + log1p(exp(-|z|)): equal to nn.BCELoss's -max(log(.), -100) of
+ *                    the f32 sigmoid while |t| <= 12 or so; beyond, the f32 sigmoid saturates (1 - d = 0 from t ~ 17: the reference
+ *                    then reports 100 and a zero gradient where this reports t and a gradient of 1 / M).
+ *                    ws: spcl_discr_head_workspace_bytes(N, H, W, C).
+ *   spcl_discr_head_backward: dt' = dt * (grad ? grad[0] : 1) (grad a device scalar).  du [N][H][W][C] (nullable) = the gradient
+ *                    w.r.t. scale x + shift (gather over the <= 16 positions that cover a pixel); dw [16 C] (nullable) = sum_m dt'
+ *                    act(.) over slabs of positions, folded in slab order.  Only what is asked for is computed. */
+int spcl_patch4s2_rows_forward(const float* a, int Ca, long a_sn, long a_sc, long a_sh, long a_sw, const float* b, int Cb,
+                               long b_sn, long b_sc, long b_sh, long b_sw, int N, int H, int W, int mode, const float* scale,
+                               const float* shift, float* rows, void* stream);
+int spcl_patch4s2_rows_backward(const float* drows, const float* x, int N, int H, int W, int C, int c_lo, int mode,
+                                const float* scale, const float* shift, float* dx, void* stream);
+size_t spcl_rows_bn_workspace_bytes(int M, int C);
+int spcl_rows_bn_forward(const float* x, int M, int C, const float* gamma, const float* beta, float eps, float momentum,
+                         float* running_mean, float* running_var, float* stats, void* ws, size_t ws_bytes, void* stream);
+int spcl_rows_bn_eval_affine(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                             float eps, int C, float* stats, void* stream);
+int spcl_rows_bn_backward(const float* du, const float* x, int M, int C, const float* gamma, const float* stats, int training,
+                          float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
+size_t spcl_discr_head_workspace_bytes(int N, int H, int W, int C);
+int spcl_discr_head_forward(const float* x, int N, int H, int W, int C, const float* scale, const float* shift, const float* w,
+                            int y, float* t, float* d, float* loss, float* dt, void* ws, size_t ws_bytes, void* stream);
+int spcl_discr_head_backward(const float* x, int N, int H, int W, int C, const float* scale, const float* shift, const float* w,
+                             const float* dt, const float* grad, float* du, float* dw, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,7 @@ _MIRRORED = {
     "semi_seg.arch": "semi_seg.arch",
     "semi_seg.arch.unet": "semi_seg.arch.unet",
     "semi_seg.arch.hook": "semi_seg.arch.hook",
+    "semi_seg.arch.discr": "semi_seg.arch.discr",
     "semi_seg.hooks": "semi_seg.hooks",
     "semi_seg.hooks.creator": "semi_seg.hooks.creator",
     "semi_seg.hooks.infonce": "semi_seg.hooks.infonce",

@@ -2935,3 +2935,283 @@ def mixup_kl_onehot(logits, target, target_tf, plan, eps=1e-16, weight=1.0):
     plan's blend of the one-hot maps of ``cat([target, target_tf])`` and of their permutation (never built); targets
     [B, 1, H, W] or [B, H, W] integer label maps"""
     return _MixupKLFn.apply(logits, target, target_tf, plan, float(eps), float(weight))
+
+
+# --------------------------------------------------------------------------------------------- DCGAN discriminator
+# (csrc/discr.hip: the adversarial baseline, semi_seg/arch/discr.py:17-36 + nn.BCELoss of new_comparable.py:124)
+DISCR_IDENTITY, DISCR_LEAKY, DISCR_BN_LEAKY = 0, 1, 2
+
+
+class RowsBN:
+    """what a training- or eval-mode ``nn.BatchNorm2d`` brings to a fused layer besides gamma / beta: its running
+    statistics (updated in place by the forward launch in training mode), momentum, eps and the mode"""
+
+    def __init__(self, running_mean, running_var, training, momentum=0.1, eps=1e-5):
+        self.running_mean, self.running_var = running_mean, running_var
+        self.training, self.momentum, self.eps = bool(training), float(momentum), float(eps)
+
+
+def _f32_map(t, name):
+    if t.dim() != 4 or t.dtype != torch.float32:
+        raise ValueError(f"{name}: a float32 [N, C, H, W] map, got {t.dtype} {tuple(t.shape)}")
+    return t.detach()
+
+
+def patch4s2_rows(x, mode=DISCR_IDENTITY, scale=None, shift=None, x2=None):
+    """patch rows [N Ho Wo, 16 C] of ``Conv2d(C, ., 4, 2, 1)`` over the logical [N, C, H, W] map ``x`` (any strides; with
+    ``x2`` the channel concatenation [x, x2], nothing is concatenated), k = 16 c + 4 kh + kw, the input transform ``mode``
+    applied on the way (include/spcl_hip.h).  No autograd."""
+    _n.require_gpu(x, x2, scale, shift)
+    x = _f32_map(x, "patch4s2_rows")
+    N, Ca, H, W = x.shape
+    Cb = 0
+    if x2 is not None:
+        x2 = _f32_map(x2, "patch4s2_rows")
+        if x2.shape[0] != N or tuple(x2.shape[2:]) != (H, W):
+            raise ValueError(f"patch4s2_rows: maps {tuple(x.shape)} and {tuple(x2.shape)} do not stack")
+        Cb = x2.shape[1]
+    C = Ca + Cb
+    if mode == DISCR_BN_LEAKY and (scale is None or scale.numel() != C or shift.numel() != C):
+        raise ValueError("patch4s2_rows: scale and shift of C elements")
+    rows = torch.empty(N * (H // 2) * (W // 2), 16 * C, dtype=torch.float32, device=x.device)
+    sa = x.stride()
+    sb = x2.stride() if x2 is not None else (0, 0, 0, 0)
+    _n.call("spcl_patch4s2_rows_forward", _n.ptr(x), Ca, sa[0], sa[1], sa[2], sa[3], _n.ptr(x2), Cb, sb[0], sb[1], sb[2], sb[3],
+            N, H, W, int(mode), _n.ptr(scale), _n.ptr(shift), _n.ptr(rows), _n.stream())
+    return rows
+
+
+def patch4s2_rows_backward(drows, shape, mode=DISCR_IDENTITY, x_store=None, scale=None, shift=None, c_lo=0):
+    """gather form of the patch rows' backward: ``drows`` [N Ho Wo, 16 C] -> [N, H, W, C - c_lo] (NHWC storage) times the
+    transform's derivative at ``x_store`` [N, H, W, C]; in BN mode the gradient w.r.t. ``scale x + shift``"""
+    _n.require_gpu(drows, x_store, scale, shift)
+    N, C, H, W = shape
+    if tuple(drows.shape) != (N * (H // 2) * (W // 2), 16 * C) or not drows.is_contiguous() or drows.dtype != torch.float32:
+        raise ValueError(f"patch4s2_rows_backward: drows {tuple(drows.shape)} for a map {tuple(shape)}")
+    if mode != DISCR_IDENTITY and (tuple(x_store.shape) != (N, H, W, C) or not x_store.is_contiguous()):
+        raise ValueError("patch4s2_rows_backward: the stored map is [N, H, W, C], contiguous")
+    dx = torch.empty(N, H, W, C - c_lo, dtype=torch.float32, device=drows.device)
+    _n.call("spcl_patch4s2_rows_backward", _n.ptr(drows), _n.ptr(x_store), N, H, W, C, int(c_lo), int(mode), _n.ptr(scale),
+            _n.ptr(shift), _n.ptr(dx), _n.stream())
+    return dx
+
+
+def _rows_bn_ws(M, C, dev):
+    nbytes = _n.call("spcl_rows_bn_workspace_bytes", M, C)
+    if nbytes == 0:
+        raise ValueError(f"rows BatchNorm: M >= 2 rows of C % 4 == 0, C <= 1024 channels (got {M}, {C})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def rows_bn_stats(x, gamma, beta, bn: RowsBN):
+    """``stats`` [4, C] = (mean, invstd, scale, shift) of a BatchNorm over the rows of ``x`` [M, C]: batch statistics (and the
+    running-statistic update, in place) in training mode, the running statistics otherwise"""
+    _n.require_gpu(x, gamma, beta, bn.running_mean, bn.running_var)
+    M, C = x.shape
+    stats = torch.empty(4, C, dtype=torch.float32, device=x.device)
+    if bn.training:
+        ws = _rows_bn_ws(M, C, x.device)
+        _n.call("spcl_rows_bn_forward", _n.ptr(x), M, C, _n.ptr(gamma), _n.ptr(beta), c_float(bn.eps), c_float(bn.momentum),
+                _n.ptr(bn.running_mean), _n.ptr(bn.running_var), _n.ptr(stats), _n.ptr(ws), ws.numel(), _n.stream())
+    else:
+        _n.call("spcl_rows_bn_eval_affine", _n.ptr(gamma), _n.ptr(beta), _n.ptr(bn.running_mean), _n.ptr(bn.running_var),
+                c_float(bn.eps), C, _n.ptr(stats), _n.stream())
+    return stats
+
+
+def rows_bn_backward(du, x, gamma, stats, training, sinks=(None, None)):
+    """from ``du`` = dLoss/d(scale x + shift) [M, C]: (dx, dgamma, dbeta) of the BatchNorm, batch terms included in
+    training mode.  ``dx`` overwrites ``du``."""
+    M, C = x.shape
+    dev = x.device
+    dgamma, dbeta = _grad_buffer(sinks[0], (C,), dev), _grad_buffer(sinks[1], (C,), dev)
+    ws = _rows_bn_ws(M, C, dev)
+    _n.call("spcl_rows_bn_backward", _n.ptr(du), _n.ptr(x), M, C, _n.ptr(gamma), _n.ptr(stats), int(bool(training)), _n.ptr(du),
+            _n.ptr(dgamma), _n.ptr(dbeta), _n.ptr(ws), ws.numel(), _n.stream())
+    return du, dgamma, dbeta
+
+
+def _rows_product(rows, w2d):
+    """y [M, Cout] = rows [M, K] w2d[Cout, K]^T on the exact-f32 rows product (no bias: the discriminator's convolutions have none)"""
+    M, K = rows.shape
+    cout = w2d.shape[0]
+    y = torch.empty(M, cout, dtype=torch.float32, device=rows.device)
+    _n.call("spcl_rows_linear_forward", _n.ptr(rows), _n.SPCL_F32, K, 0, _n.ptr(w2d), None, M, K, cout, _n.ptr(y), _n.stream())
+    return y
+
+
+def _rows_product_backward(g, w2d, rows, sink):
+    """(drows [M, K], dW [Cout, K] or None when ``rows`` is None: a pass that keeps no weight gradient computes none)"""
+    M, cout = g.shape
+    K = w2d.shape[1]
+    dev = g.device
+    drows = torch.empty(M, K, dtype=torch.float32, device=dev)
+    _n.call("spcl_rows_linear_backward_input", _n.ptr(g), _n.SPCL_F32, _n.ptr(w2d), None, M, cout, K, _n.ptr(drows), _n.SPCL_F32, K,
+            _n.stream())
+    dw = None
+    if rows is not None:
+        dw = _grad_buffer(sink, (cout, K), dev)
+        ws = torch.empty(_n.call("spcl_rows_linear_backward_weight_workspace_bytes", M, cout, K) // 4 + 1, dtype=torch.float32,
+                         device=dev)
+        _n.call("spcl_rows_linear_backward_weight", _n.ptr(g), _n.SPCL_F32, _n.ptr(rows), _n.SPCL_F32, K, 0, M, cout, K, _n.ptr(ws),
+                ws.numel() * 4, _n.ptr(dw), None, _n.stream())
+    return drows, dw
+
+
+def _conv4_weight(w, C):
+    """the contiguous [Cout, C, 4, 4] parameter as the product's [Cout, 16 C] matrix (a view: the k order is the parameter's)"""
+    if w.dim() != 4 or tuple(w.shape[1:]) != (C, 4, 4) or w.dtype != torch.float32:
+        raise ValueError(f"a float32 [Cout, {C}, 4, 4] convolution weight, got {w.dtype} {tuple(w.shape)}")
+    if w.shape[0] % 4 != 0:
+        raise ValueError(f"the rows product needs Cout % 4 == 0 (got {w.shape[0]}): hidden_dim must be a multiple of 4")
+    return w.detach().contiguous().view(w.shape[0], 16 * C)
+
+
+class _DiscrConvFn(torch.autograd.Function):
+    """``Conv2d(C, Cout, 4, 2, 1, bias=False)`` over ``T(x)``, T the identity (discr.py:19; ``x2``: the class map behind the
+    image ``x``, which gets no gradient) or LeakyReLU(0.2) of the stored pre-activation ``x`` (discr.py:20-22): patch rows +
+    rows product.  Returns the pre-activation map, logical [N, Cout, Ho, Wo] on NHWC storage.  ``need_w`` False: no weight
+    gradient is computed and the patch rows are not kept."""
+
+    @staticmethod
+    def forward(ctx, x, x2, weight, mode, need_w):
+        _n.require_gpu(x, x2, weight)
+        N, Ca, H, W = x.shape
+        C = Ca + (x2.shape[1] if x2 is not None else 0)
+        w2d = _conv4_weight(weight, C)
+        xs = _class_map_storage(x.detach()) if mode == DISCR_LEAKY else None  # (kept for LeakyReLU')
+        src = xs.permute(0, 3, 1, 2) if xs is not None else x
+        rows = patch4s2_rows(src, mode, x2=x2)
+        y = _rows_product(rows, w2d)
+        ctx.save_for_backward(xs, w2d, rows if need_w else None)
+        ctx.meta = (N, C, H, W, Ca if x2 is not None else 0, mode)
+        ctx.weight = weight
+        return y.view(N, H // 2, W // 2, w2d.shape[0]).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xs, w2d, rows = ctx.saved_tensors
+        N, C, H, W, c_lo, mode = ctx.meta
+        g = _class_map_storage(dy.detach())
+        g = g.view(-1, g.shape[3])
+        ng = ctx.needs_input_grad
+        want_w = rows is not None and ng[2]
+        drows, dw = _rows_product_backward(g, w2d, rows if want_w else None, take_grad_sink(ctx.weight, want_w))
+        dx = None
+        if ng[1] if c_lo else ng[0]:
+            dx = patch4s2_rows_backward(drows, (N, C, H, W), mode, xs, c_lo=c_lo).permute(0, 3, 1, 2)
+        dwv = None if dw is None else dw.view(ctx.weight.shape)
+        return (None, dx, dwv, None, None) if c_lo else (dx, None, dwv, None, None)
+
+
+class _DiscrBnConvFn(torch.autograd.Function):
+    """``BatchNorm2d -> LeakyReLU(0.2) -> Conv2d(C, Cout, 4, 2, 1, bias=False)`` of the stored pre-BN map ``x`` (discr.py:23-26,
+    27-30): one statistics launch, patch rows with the affine + activation applied on read, rows product.  Backward: the
+    full BatchNorm gradient (mean and variance terms) in training mode."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, weight, bn: RowsBN, need_w):
+        _n.require_gpu(x, gamma, beta, weight)
+        N, C, H, W = x.shape
+        w2d = _conv4_weight(weight, C)
+        xs = _class_map_storage(x.detach())
+        gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
+        stats = rows_bn_stats(xs.view(-1, C), gm, bt, bn)
+        rows = patch4s2_rows(xs.permute(0, 3, 1, 2), DISCR_BN_LEAKY, stats[2], stats[3])
+        y = _rows_product(rows, w2d)
+        ctx.save_for_backward(xs, gm, stats, w2d, rows if need_w else None)
+        ctx.meta = (N, C, H, W, bn.training, need_w)
+        ctx.params = (gamma, beta, weight)
+        return y.view(N, H // 2, W // 2, w2d.shape[0]).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xs, gm, stats, w2d, rows = ctx.saved_tensors
+        N, C, H, W, training, need_w = ctx.meta
+        gamma, beta, weight = ctx.params
+        g = _class_map_storage(dy.detach())
+        g = g.view(-1, g.shape[3])
+        ng = ctx.needs_input_grad
+        want_w = rows is not None and ng[3]
+        drows, dw = _rows_product_backward(g, w2d, rows if want_w else None, take_grad_sink(weight, want_w))
+        du = patch4s2_rows_backward(drows, (N, C, H, W), DISCR_BN_LEAKY, xs, stats[2], stats[3])
+        sinks = (take_grad_sink(gamma, need_w and ng[1]), take_grad_sink(beta, need_w and ng[2]))
+        dx, dgamma, dbeta = rows_bn_backward(du.view(-1, C), xs.view(-1, C), gm, stats, training, sinks)
+        if not need_w:
+            dgamma = dbeta = None
+        return (dx.view(N, H, W, C).permute(0, 3, 1, 2), dgamma, dbeta, None if dw is None else dw.view(weight.shape), None,
+                None)
+
+
+class _DiscrBnHeadFn(torch.autograd.Function):
+    """``BatchNorm2d -> LeakyReLU(0.2) -> Conv2d(C, 1, 4, 1, 0, bias=False) -> Sigmoid`` of the stored pre-BN map ``x``
+    (discr.py:31-35) and, with ``label`` 0 or 1, ``nn.BCELoss()(., label)`` (new_comparable.py:124,162-163,183-191) in the same
+    launch.  Returns the loss (a 0-dim tensor) or, with ``label`` None, sigmoid(t) [N, 1, H - 3, W - 3]."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, weight, bn: RowsBN, label, need_w):
+        _n.require_gpu(x, gamma, beta, weight)
+        N, C, H, W = x.shape
+        if tuple(weight.shape) != (1, C, 4, 4) or weight.dtype != torch.float32:
+            raise ValueError(f"the head's weight is float32 [1, {C}, 4, 4], got {tuple(weight.shape)}")
+        if label is not None and label not in (0, 1):
+            raise ValueError(f"the BCE target is the constant 0 or 1, got {label!r}")
+        dev = x.device
+        xs = _class_map_storage(x.detach())
+        gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
+        w1d = weight.detach().contiguous().view(-1)
+        stats = rows_bn_stats(xs.view(-1, C), gm, bt, bn)
+        nbytes = _n.call("spcl_discr_head_workspace_bytes", N, H, W, C)
+        if nbytes == 0:
+            raise ValueError(f"discriminator head: a map of at least 4 x 4 with C % 4 == 0 (got {H} x {W}, C = {C})")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        M = N * (H - 3) * (W - 3)
+        t, d = torch.empty(M, dtype=torch.float32, device=dev), torch.empty(M, dtype=torch.float32, device=dev)
+        loss = dt = None
+        if label is not None:
+            loss, dt = torch.empty((), dtype=torch.float32, device=dev), torch.empty(M, dtype=torch.float32, device=dev)
+        _n.call("spcl_discr_head_forward", _n.ptr(xs), N, H, W, C, _n.ptr(stats[2]), _n.ptr(stats[3]), _n.ptr(w1d),
+                -1 if label is None else int(label), _n.ptr(t), _n.ptr(d), _n.ptr(loss), _n.ptr(dt), _n.ptr(ws), ws.numel(),
+                _n.stream())
+        ctx.save_for_backward(xs, gm, stats, w1d, dt if label is not None else d)
+        ctx.meta = (N, C, H, W, bn.training, need_w, label is not None)
+        ctx.params = (gamma, beta, weight)
+        return loss if label is not None else d.view(N, 1, H - 3, W - 3)
+
+    @staticmethod
+    def backward(ctx, gout):
+        xs, gm, stats, w1d, saved = ctx.saved_tensors
+        N, C, H, W, training, need_w, is_loss = ctx.meta
+        gamma, beta, weight = ctx.params
+        dev = xs.device
+        ng = ctx.needs_input_grad
+        if is_loss:
+            dt, grad = saved, (None if is_unit_gradient(gout) else gout.detach().float().reshape(1).contiguous())
+        else:  # d sigmoid(t) = d (1 - d): M elements, not a hot path (the epocher goes through the loss)
+            dt, grad = (gout.detach().float().reshape(-1) * saved * (1.0 - saved)).contiguous(), None
+        want_w = need_w and ng[3]
+        du = torch.empty(N, H, W, C, dtype=torch.float32, device=dev)
+        dw = _grad_buffer(take_grad_sink(weight, want_w), (16 * C,), dev) if want_w else None
+        ws = torch.empty(_n.call("spcl_discr_head_workspace_bytes", N, H, W, C), dtype=torch.uint8, device=dev)
+        _n.call("spcl_discr_head_backward", _n.ptr(xs), N, H, W, C, _n.ptr(stats[2]), _n.ptr(stats[3]), _n.ptr(w1d), _n.ptr(dt),
+                _n.ptr(grad), _n.ptr(du), _n.ptr(dw), _n.ptr(ws), ws.numel(), _n.stream())
+        sinks = (take_grad_sink(gamma, need_w and ng[1]), take_grad_sink(beta, need_w and ng[2]))
+        dx, dgamma, dbeta = rows_bn_backward(du.view(-1, C), xs.view(-1, C), gm, stats, training, sinks)
+        if not need_w:
+            dgamma = dbeta = None
+        return (dx.view(N, H, W, C).permute(0, 3, 1, 2), dgamma, dbeta, None if dw is None else dw.view(weight.shape), None,
+                None, None)
+
+
+def discr_conv(x, weight, *, leaky_in=False, x2=None, weight_grads=True):
+    """``Conv2d(., ., 4, 2, 1, bias=False)`` of ``x`` (``leaky_in``: of LeakyReLU(0.2)(x)); ``x2``: stacked behind ``x``, which
+    then gets no gradient (the image in front of a class map)"""
+    return _DiscrConvFn.apply(x, x2, weight, DISCR_LEAKY if leaky_in else DISCR_IDENTITY, bool(weight_grads))
+
+
+def discr_bn_conv(x, gamma, beta, weight, bn: RowsBN, *, weight_grads=True):
+    return _DiscrBnConvFn.apply(x, gamma, beta, weight, bn, bool(weight_grads))
+
+
+def discr_bn_head(x, gamma, beta, weight, bn: RowsBN, *, label=None, weight_grads=True):
+    return _DiscrBnHeadFn.apply(x, gamma, beta, weight, bn, label, bool(weight_grads))

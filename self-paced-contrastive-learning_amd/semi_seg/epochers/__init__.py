@@ -2,3 +2,4 @@ from .pretrain import PretrainDecoderEpocher, PretrainEncoderEpocher, unzip_twic
 from .finetune import EvalEpocher, FineTuneEpocher  # noqa: F401
 from .legacy import ContrastiveProjectorWrapper, InfoNCEPretrainEpocher  # noqa: F401
 from .semi import SemiSupervisedEpocher  # noqa: F401
+from .adversarial import AdversarialEpocher  # noqa: F401

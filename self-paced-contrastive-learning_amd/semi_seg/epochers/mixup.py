@@ -80,3 +80,7 @@ class MixUpEpocher(SemiSupervisedEpocher):
             dice = self.meters["sup_dice"]
             dice.add_counts(inter, union, dice.group_names_for(inter.shape[0], list(label_group)))
         return sup_loss, reg_loss
+
+
+# the reference's ``new_comparable`` module also holds the adversarial epocher
+from .adversarial import AdversarialEpocher  # noqa: E402,F401

@@ -1,3 +1,3 @@
 from .pretrain import PretrainDecoderTrainer, PretrainEncoderTrainer, WarmupCosine  # noqa: F401
 from .finetune import FineTuneTrainer  # noqa: F401
-from .semi import MixUpTrainer, SemiTrainer  # noqa: F401
+from .semi import AdversarialTrainer, MixUpTrainer, SemiTrainer  # noqa: F401

@@ -139,4 +139,4 @@ class FineTuneTrainer:
 
 
 # the reference's ``new_trainer`` module also holds these (``main.py:15`` imports all three from it)
-from .semi import MixUpTrainer, SemiTrainer  # noqa: E402,F401
+from .semi import AdversarialTrainer, MixUpTrainer, SemiTrainer  # noqa: E402,F401

@@ -2,11 +2,14 @@
 best / last checkpoints with the hook registry of the pre-train trainer -- ``register_hooks`` before ``init()``, one flat
 parameter over model + hook parameters, ``__hooks__`` in the checkpoint -- and ``SemiSupervisedEpocher`` as the training
 epocher (``two_stage`` / ``disable_bn`` from the reference's keyword set).  ``MixUpTrainer`` (:67-72) is the same trainer on
-``MixUpEpocher`` (semi_seg/epochers/mixup.py): the labelled loader alone, the mix-up hook as its regulariser."""
+``MixUpEpocher`` (semi_seg/epochers/mixup.py): the labelled loader alone, the mix-up hook as its regulariser.
+``AdversarialTrainer`` (:75-120) adds a second network, the DCGAN discriminator, with a flat parameter and an optimizer of
+its own, and runs ``AdversarialEpocher`` (semi_seg/epochers/adversarial.py) without hooks."""
 import torch
 from torch import nn
 
 from ... import ddp as _ddp
+from ..epochers.adversarial import AdversarialEpocher
 from ..epochers.mixup import MixUpEpocher
 from ..epochers.semi import SemiSupervisedEpocher
 from .finetune import FineTuneTrainer
@@ -89,3 +92,66 @@ class MixUpTrainer(SemiTrainer):
     @property
     def train_epocher(self):
         return MixUpEpocher
+
+
+class AdversarialTrainer(SemiTrainer):
+    """``AdversarialTrainer`` (new_trainer.py:75-120): ``SemiTrainer`` without hooks on ``AdversarialEpocher``, plus the
+    discriminator (``Discriminator(input_dim, hidden_dim=64)`` built under the configured ``RandomSeed``, ``input_dim`` = the
+    classes, plus the image channels with ``dis_consider_image``) and its optimizer, built from ``config["Optim"]`` like the
+    model's.  That optimizer gets NO scheduler: the discriminator's learning rate stays at ``Optim.lr`` while the model's
+    follows the warm-up / cosine schedule (the reference builds ``_dis_optimizer`` by hand, :100-103, outside
+    ``_init_scheduler``).  The checkpoint carries both under the names the reference's automatic buffer gives them,
+    ``_discriminator`` and ``_dis_optimizer``."""
+    activate_hooks = False
+
+    def __init__(self, **kwargs):
+        if not kwargs:  # (as MixUpTrainer: no default construction)
+            raise NotImplementedError("AdversarialTrainer: no default construction (pass model=, the loaders, criterion=, "
+                                      "reg_weight=, ...)")
+        if "reg_weight" not in kwargs:
+            raise TypeError("AdversarialTrainer.__init__() missing 1 required keyword-only argument: 'reg_weight'")
+        reg_weight = kwargs.pop("reg_weight")
+        dis_consider_image = bool(kwargs.pop("dis_consider_image", False))
+        super().__init__(**kwargs)
+        from ...val import fix_all_seed_within_context
+        from ..arch.discr import Discriminator
+        input_dim = self._model.num_classes + (self._model._input_dim if dis_consider_image else 0)
+        self._dis_consider_image = dis_consider_image
+        seed = (self._config or {}).get("RandomSeed", 10)
+        with fix_all_seed_within_context(seed):
+            self._discriminator = Discriminator(input_dim=input_dim, hidden_dim=64)
+        self._reg_weight = float(reg_weight)
+        self._dis_optimizer = self._dis_flat = None
+
+    def init(self):
+        super().init()
+        self._discriminator.to(self._device)
+        _ddp.broadcast_state(self._discriminator)
+        self._dis_flat = _ddp.FlatParams([p for p in self._discriminator.parameters() if p.requires_grad])
+        self._dis_optimizer = build_optimizer(self._optim_name, self._dis_flat.param, self._optim_cfg)  # (no scheduler)
+
+    @property
+    def train_epocher(self):
+        return AdversarialEpocher
+
+    def _create_tra_epoch(self):
+        epocher = self.train_epocher(model=self._model, optimizer=self._optimizer, labeled_loader=self._labeled_loader,
+                                     unlabeled_loader=self._unlabeled_loader, sup_criterion=self._criterion,
+                                     num_batches=self._num_batches, cur_epoch=self._cur_epoch, device=self._device,
+                                     two_stage=self._two_stage, disable_bn=self._disable_bn, flat_params=self._flat,
+                                     discriminator=self._discriminator, discr_optimizer=self._dis_optimizer,
+                                     reg_weight=self._reg_weight, dis_consider_image=self._dis_consider_image,
+                                     discr_flat_params=self._dis_flat)
+        epocher.init()
+        return epocher
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["_discriminator"] = self._discriminator.state_dict()
+        sd["_dis_optimizer"] = self._dis_optimizer.state_dict()
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        self._discriminator.load_state_dict(sd["_discriminator"])
+        self._dis_optimizer.load_state_dict(sd["_dis_optimizer"])
