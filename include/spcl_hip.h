@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 15
+#define SPCL_ABI_VERSION 16
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -568,6 +568,27 @@ int spcl_one_hot(const int64_t* labels, size_t npix, int K, float* out, void* st
 int spcl_argmax_classes(const float* logits, size_t npix, int K, int64_t* out, void* stream);
 int spcl_dice_counts(const int64_t* pred, const int64_t* target, int B, int per_sample, int C, int64_t* inter_zeroed,
                      int64_t* union_zeroed, void* stream);
+
+/* Surface distances of two class-coded maps (csrc/surface.hip): replaces SurfaceMeter._evalue
+ * (contrastyou/meters/surface_meter.py:109-128: one host call per (slice, class)) and the three functions it dispatches to
+ * (contrastyou/meters/surface_distance.py: hausdorff_distance, mod_hausdorff_distance, average_surface_distance -- medpy's
+ * erosion + exact Euclidean distance transform + gather, restated from their definition).
+ *   pred, target  [B][H][W] int64 class-coded maps;  report: n_report (<= 64) HOST ints, the classes to evaluate, each in [0, C)
+ *   per (b, r): A = (pred[b] == report[r]), T = (target[b] == report[r]);  border(m) = the pixels of m with a 4-neighbour outside
+ *   m or outside the image;  sds(A, T) = for every border pixel of A the distance sqrt((dy sy)^2 + (dx sx)^2) to the nearest
+ *   border pixel of T
+ *   hd   [B][n_report] f64  max(max sds(A, T), max sds(T, A))
+ *   mhd  [B][n_report] f64  max(P(sds(A, T)), P(sds(T, A))), P = numpy's linear percentile at `percentile` (0 .. 100)
+ *   asd  [B][n_report] f64  (mean sds(A, T) + mean sds(T, A)) / 2
+ *   empty[B][n_report] u8   1 where A or T has no pixel (medpy raises there); hd, mhd and asd are NaN at those entries
+ * The transform is exact (separable two-pass; integer squared distances under unit spacing, one f64 sqrt at the end), its cost
+ * H W (H + W) per pair whatever the masks look like; the means are summed in a fixed order (same input, same bits).  H, W <= 1024.
+ * ws: spcl_surface_workspace_bytes(B, H, W, n_report) bytes, 16-byte aligned (0 = unsupported shape).  Four launches on
+ * `stream`, nothing is read back. */
+size_t spcl_surface_workspace_bytes(int B, int H, int W, int n_report);
+int spcl_surface_distances(const int64_t* pred, const int64_t* target, int B, int H, int W, int C, const int* report,
+                           int n_report, double sy, double sx, double percentile, double* hd, double* mhd, double* asd,
+                           uint8_t* empty, void* ws, size_t ws_bytes, void* stream);
 
 /* Decoder data movement (NHWC, CS a multiple of 16): nn.Upsample(scale_factor=2) of `_UpConv` (unet.py:89) and its
  * backward (H, W = the low-resolution size in both calls), torch.cat((skip, up), dim=1) (unet.py:194-224) and its

@@ -1,7 +1,8 @@
 """Minimal meters for the hot path (the reference's ``contrastyou/meters`` package is out of scope): the
 three meter names the InfoNCE hooks write (``loss``, ``sp_weight``, ``age_param``) plus ``reg_loss``/``lr``.
 Values may be device tensors: they are accumulated ON DEVICE and read back once, in ``summary()`` -- the reference's
-per-step ``.item()`` synchronisations (K19) disappear."""
+per-step ``.item()`` synchronisations (K19) disappear.  ``UniversalDice`` and ``SurfaceMeter`` (evaluation / inference)
+keep per-sample device results the same way."""
 from collections import OrderedDict
 from contextlib import contextmanager
 
@@ -244,3 +245,91 @@ class UniversalDice:
 
     def __repr__(self):
         return f"C={self._C}, report_axis={self._report_axis}\n\t{self.summary()}"
+
+
+class SurfaceMeter:
+    """Mirror of ``contrastyou/meters/surface_meter.py:21-149``: Hausdorff (``hausdorff``), percentile-95 Hausdorff
+    (``mod_hausdorff``) or average surface distance (``average_surface``) per slice and reported class, mean / std over
+    all recorded (sample, class) rows, ``summary()`` with ``HD{i}`` / ``MHD{i}`` / ``ASD{i}``.
+
+    ``add(pred, target, voxelspacing)`` is ONE HIP call (``functional.surface_distances``: an exact distance transform on
+    the device, no medpy) whose [B, n_report] values and empty-class flags stay on the device; nothing is read back before
+    ``value()`` / ``summary()``.  Where the reference's ``add`` raises ``RuntimeError`` (a reported class missing from a
+    slice of ``pred`` or ``target``; ``InferenceEpocher`` ignores it, so that batch is not recorded,
+    semi_seg/epochers/base.py:120-121), this meter records the flags and ``value()`` leaves the whole batch out -- the same
+    statistics; ``skipped_batches`` counts them, ``add(..., raise_on_empty=True)`` reads the flags back and raises as the
+    reference does.  Class-coded integer maps are taken as they are; a ``[B,C,H,W]`` pair (simplex prediction, one-hot
+    target) is reduced with ``functional.argmax_classes`` first."""
+    meter_choices = {"mod_hausdorff": "mhd", "hausdorff": "hd", "average_surface": "asd"}  # name -> output of the HIP call
+    abbr = {"mod_hausdorff": "MHD", "hausdorff": "HD", "average_surface": "ASD"}
+
+    def __init__(self, C=4, report_axises=None, metername: str = "hausdorff") -> None:
+        assert report_axises is None or isinstance(report_axises, (list, tuple)), \
+            f"`report_axises` should be either None or an iterator, given {type(report_axises)}"
+        if report_axises is not None:
+            assert max(report_axises) <= C, "Incompatible parameter of `C`={} and `report_axises`={}".format(
+                C, report_axises)
+        self._C = C
+        self._report_axis = list(range(self._C)) if report_axises is None else report_axises
+        assert metername in self.meter_choices.keys()
+        self._surface_name = metername
+        self._abbr = self.abbr[metername]
+        self.reset()
+
+    def reset(self):
+        self._values, self._empty = [], []
+        self._n = 0
+
+    def add(self, pred, target, voxelspacing=None, raise_on_empty=False):
+        from .. import functional as F_hip
+        assert pred.shape == target.shape, \
+            f"incompatible shape of `pred` and `target`, given {pred.shape} and {target.shape}."
+        assert not pred.requires_grad and not target.requires_grad
+        if pred.dim() == 4:  # simplex prediction + one-hot target (``_convert2onehot``): back to class codes
+            pred, target = F_hip.argmax_classes(pred.float()), F_hip.argmax_classes(target.float())
+        hd, mhd, asd, empty = F_hip.surface_distances(pred, target, self._C, self._report_axis, voxelspacing, 95.0)
+        if raise_on_empty and bool(empty.any()):
+            raise RuntimeError("The first or the second supplied array does not contain any binary object.")
+        self._values.append({"hd": hd, "mhd": mhd, "asd": asd}[self.meter_choices[self._surface_name]])
+        self._empty.append(empty)
+        self._n += 1
+
+    def _rows(self):
+        """-> ([rows, n_report] float64 array of the recorded batches, number of batches left out): the one read-back"""
+        import numpy as np
+        sizes = [v.shape[0] for v in self._values]
+        vals = torch.cat(self._values, 0).cpu().numpy()
+        flags = torch.cat(self._empty, 0).cpu().numpy()
+        keep, skipped, o = [], 0, 0
+        for n in sizes:
+            if flags[o:o + n].any():
+                skipped += 1
+            else:
+                keep.append(vals[o:o + n])
+            o += n
+        rows = np.concatenate(keep, 0) if keep else np.zeros((0, vals.shape[1]))
+        return rows, skipped
+
+    @property
+    def skipped_batches(self):
+        """how many recorded batches hold an empty reported class and are left out of ``value()`` (reads the flags back)"""
+        return self._rows()[1] if self._n else 0
+
+    def value(self, **kwargs):
+        nan = ([float("nan")] * self._C, [float("nan")] * self._C)
+        if self._n == 0:
+            return nan
+        rows, _ = self._rows()
+        if rows.shape[0] == 0:  # every batch was left out: what the reference reports when every ``add`` raised
+            return nan
+        return rows.mean(0), rows.std(0)
+
+    def summary(self) -> dict:
+        means, _ = self.value()
+        return {f"{self._abbr}{i}": float(means[num]) for num, i in enumerate(self._report_axis)}
+
+    def get_plot_names(self):
+        return [f"{self._abbr}{i}" for i in self._report_axis]
+
+    def __repr__(self):
+        return f"C={self._C}, report_axis={self._report_axis}\n\t" + "\t".join(f"{k}:{v}" for k, v in self.summary().items())

@@ -2418,6 +2418,45 @@ def dice_counts(pred: torch.Tensor, target: torch.Tensor, C: int):
     return inter, union
 
 
+_SURFACE_WS = {}  # (device, B, H, W, n_report) -> workspace; every call on that shape reuses it (calls are stream-ordered)
+
+
+def surface_distances(pred: torch.Tensor, target: torch.Tensor, C: int, report_axis=None, voxelspacing=None,
+                      percentile: float = 95.0):
+    """Hausdorff, percentile Hausdorff and average surface distance per (sample, reported class) of two class-coded [B,H,W]
+    maps (``spcl_surface_distances``) -> ``(hd, mhd, asd, empty)``: three float64 [B, n_report] tensors and a uint8 flag that
+    is set where the class is missing from ``pred`` or ``target`` (the three values are NaN there).  ``voxelspacing``: None
+    (1, 1), one float for both axes, or ``(sy, sx)``.  Everything stays on the device."""
+    _n.require_gpu(pred, target)
+    if pred.shape != target.shape:
+        raise AssertionError(f"incompatible shape of `pred` and `target`, given {pred.shape} and {target.shape}.")
+    if pred.dim() != 3 or pred.is_floating_point() or target.is_floating_point():
+        raise TypeError(f"surface_distances takes class-coded integer [B,H,W] maps, given {tuple(pred.shape)} {pred.dtype}")
+    report = list(range(C)) if report_axis is None else [int(c) for c in report_axis]
+    if voxelspacing is None:
+        sy = sx = 1.0
+    elif isinstance(voxelspacing, (int, float)):
+        sy = sx = float(voxelspacing)
+    else:
+        sy, sx = (float(v) for v in voxelspacing)
+    p, t = pred.detach().long().contiguous(), target.detach().long().contiguous()
+    B, H, W = p.shape
+    R, dev = len(report), p.device
+    key = (dev, B, H, W, R)
+    ws = _SURFACE_WS.get(key)
+    if ws is None:
+        nbytes = _n.call("spcl_surface_workspace_bytes", B, H, W, R)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None  # (0: the call below says why)
+        if ws is not None:
+            _SURFACE_WS[key] = ws
+    vals = torch.empty((3, B, R), dtype=torch.float64, device=dev)
+    empty = torch.empty((B, R), dtype=torch.uint8, device=dev)
+    _n.call("spcl_surface_distances", _n.ptr(p), _n.ptr(t), B, H, W, int(C), (c_int * max(R, 1))(*report), R, sy, sx,
+            float(percentile), _n.ptr(vals[0]), _n.ptr(vals[1]), _n.ptr(vals[2]), _n.ptr(empty), _n.ptr(ws),
+            ws.numel() if ws is not None else 0, _n.stream())
+    return vals[0], vals[1], vals[2], empty
+
+
 class _Upsample2xFn(torch.autograd.Function):
     """nn.Upsample(scale_factor=2) (nearest) of ``_UpConv`` on NHWC storage; backward = 2x2 sum."""
 

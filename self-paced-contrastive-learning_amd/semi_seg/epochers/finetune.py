@@ -1,5 +1,6 @@
-"""Mirror of the fine-tune / evaluation epochers: ``EvalEpocher`` (semi_seg/epochers/new_epocher.py:56-97) and
-``FineTuneEpocher`` (:241-289; the labelled-only branch of ``SemiSupervisedEpocher``).  Same control flow and meters
+"""Mirror of the fine-tune / evaluation epochers: ``EvalEpocher`` (semi_seg/epochers/new_epocher.py:56-97),
+``InferenceEpocher`` (semi_seg/epochers/base.py:93-125) and ``FineTuneEpocher`` (new_epocher.py:241-289; the labelled-only
+branch of ``SemiSupervisedEpocher``).  Same control flow and meters
 (``sup_loss``, ``sup_dice`` / ``loss``, ``dice``); the network, softmax, KL_div, arg-max and Dice counts are HIP
 kernels and the meters take device values (no per-step ``.item()``)."""
 import os
@@ -14,7 +15,7 @@ from ... import native as _n
 from ... import stepgraph as _sg
 from ...contrastyou.losses.kl import KL_div, class2one_hot
 from ...contrastyou import meters as _meters
-from ...contrastyou.meters import AverageValueMeter, MeterInterface, UniversalDice
+from ...contrastyou.meters import AverageValueMeter, MeterInterface, SurfaceMeter, UniversalDice
 
 _FUSED_SUP_LOSS = os.environ.get("SPCL_FUSED_SUP_LOSS", "1") != "0"  # A/B switch: 0 = the seven separate launches
 
@@ -129,11 +130,16 @@ class EvalEpocher(_EpocherBase):
 
     def _batch(self, eval_img, eval_target):
         """one validation batch (new_epocher.py:84-90) -> (loss, per-sample intersections, unions)"""
+        return self._batch_with_prediction(eval_img, eval_target)[:3]
+
+    def _batch_with_prediction(self, eval_img, eval_target):
+        """``_batch`` and the arg-max map its Dice counts were taken from -> (loss, intersections, unions, prediction)"""
         eval_logits = self._model(eval_img)
         onehot_target = class2one_hot(eval_target.squeeze(1), self.num_classes)
         eval_loss = self._sup_criterion(F_hip.softmax_classes(eval_logits), onehot_target, disable_assert=True)
-        inter, union = F_hip.dice_counts(F_hip.argmax_classes(eval_logits), eval_target.squeeze(1), self.num_classes)
-        return eval_loss, inter, union
+        prediction = F_hip.argmax_classes(eval_logits)
+        inter, union = F_hip.dice_counts(prediction, eval_target.squeeze(1), self.num_classes)
+        return eval_loss, inter, union, prediction
 
     def _batch_replayed(self, graphs, eval_img, eval_target):
         """``_batch`` from a hipGraph of this shape: first sight eager (lazily created workspaces are then outside any
@@ -187,6 +193,41 @@ class EvalEpocher(_EpocherBase):
             self.meters["loss"].add(eval_loss)
             dice = self.meters["dice"]
             dice.add_counts(inter, union, dice.group_names_for(inter.shape[0], list(group)))
+
+
+class InferenceEpocher(EvalEpocher):
+    """``InferenceEpocher`` (semi_seg/epochers/base.py:93-125): the evaluation pass of ``Trainer.inference()`` -- the
+    parent's loss and Dice, fed exactly as ``EvalEpocher`` feeds them, plus ``hd``, the Hausdorff distance of every slice
+    and foreground class (``SurfaceMeter``, one HIP call per batch, read back in ``summary()``), and the PNGs
+    ``save_dir/{img,gt,pred}/<file_path>.png`` (image x 255, label map, arg-max map).  The PNG writes make the pass
+    host-bound, so every batch is issued eagerly instead of through the validation hipGraphs.  A batch in which a
+    foreground class is missing from a slice does not count towards ``hd`` (the reference ignores the meter's
+    ``RuntimeError`` there)."""
+
+    def init(self, *, save_dir: str):
+        self._save_dir = str(save_dir)
+
+    def configure_meters(self, meters):
+        meters = super().configure_meters(meters)
+        C = self.num_classes
+        meters.register_meter("hd", SurfaceMeter(C=C, report_axises=list(range(1, C)), metername="hausdorff"))
+        return meters
+
+    @torch.no_grad()
+    def _run_eval(self):
+        from .helper import write_img_target, write_predict
+        if getattr(self, "_save_dir", None) is None:
+            raise RuntimeError("InferenceEpocher: call init(save_dir=...) first")
+        assert self._model.training is False, self._model.training
+        for self.cur_batch_num, eval_data in zip(range(self._num_batches), self._loader):
+            eval_img, eval_target, file_path, _, group = unzip_single_transformed(eval_data, self._device)
+            eval_loss, inter, union, prediction = self._batch_with_prediction(eval_img, eval_target)
+            write_img_target(eval_img, eval_target, self._save_dir, file_path)
+            write_predict(prediction, self._save_dir, file_path)
+            self.meters["loss"].add(eval_loss)
+            dice = self.meters["dice"]
+            dice.add_counts(inter, union, dice.group_names_for(inter.shape[0], list(group)))
+            self.meters["hd"].add(prediction, eval_target.squeeze(1))
 
 
 class FineTuneEpocher(_EpocherBase):

@@ -160,3 +160,42 @@ class TensorRandomFlip:
         for dims, idx in plan:
             res.index_copy_(0, idx, x.index_select(0, idx).flip(dims))
         return res
+
+
+def _write_pngs(maps: torch.Tensor, folder: str, filenames):
+    """[B,H,W] -> ``folder/<name>.png`` as 8-bit grey (values cast to uint8 as numpy's ``astype`` does); one read-back"""
+    import os
+
+    from PIL import Image
+    assert maps.dim() == 3 and len(filenames) == maps.shape[0], (tuple(maps.shape), len(filenames))
+    arr = maps.detach().to(torch.uint8).cpu().numpy()
+    for a, f in zip(arr, filenames):
+        path = os.path.join(folder, f + ".png")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        Image.fromarray(a, mode="L").save(path)
+
+
+def write_predict(predict_logit: torch.Tensor, save_dir: str, filenames):
+    """``write_predict`` (semi_seg/epochers/helper.py:78-85): the arg-max map of every sample to ``save_dir/pred``.  A
+    [B,K,H,W] class map is reduced with the HIP arg-max; a [B,H,W] integer map is taken as the arg-max already formed."""
+    import os
+    if isinstance(filenames, str):
+        filenames = [filenames]
+    if predict_logit.dim() == 4:
+        from ... import functional as F_hip
+        predict_logit = F_hip.argmax_classes(predict_logit)
+    assert predict_logit.dim() == 3 and not predict_logit.is_floating_point(), predict_logit.shape
+    _write_pngs(predict_logit, os.path.join(save_dir, "pred"), list(filenames))
+
+
+def write_img_target(image: torch.Tensor, target: torch.Tensor, save_dir: str, filenames):
+    """``write_img_target`` (semi_seg/epochers/helper.py:88-97): ``image * 255`` to ``save_dir/img`` and the label map to
+    ``save_dir/gt``, one PNG per sample ([B,1,H,W] or [B,H,W] tensors)"""
+    import os
+    if isinstance(filenames, str):
+        filenames = [filenames]
+    image = image.squeeze(1) if image.dim() == 4 else image
+    target = target.squeeze(1) if target.dim() == 4 else target
+    assert image.shape == target.shape, (tuple(image.shape), tuple(target.shape))
+    _write_pngs(image * 255, os.path.join(save_dir, "img"), list(filenames))
+    _write_pngs(target, os.path.join(save_dir, "gt"), list(filenames))

@@ -14,7 +14,7 @@ from torch import nn
 
 from ... import ddp as _ddp
 from ...optim import FusedRAdam
-from ..epochers.finetune import EvalEpocher, FineTuneEpocher
+from ..epochers.finetune import EvalEpocher, FineTuneEpocher, InferenceEpocher
 from .pretrain import WarmupCosine, build_optimizer, read_optim_sched
 
 
@@ -116,6 +116,37 @@ class FineTuneTrainer:
         finally:
             _sg.gc_release()  # (the epochers' captures keep the collector's heap frozen from one epoch to the next)
         return self.history
+
+    def inference(self, checkpoint=None):
+        """``Trainer.inference`` (semi_seg/trainers/base.py:127-148): load the model of a checkpoint -- ``None``: this
+        trainer's ``save_dir/best.pth``; a ``.pth`` file; or a directory holding a ``best.pth`` --, run ``InferenceEpocher``
+        over the test loader (loss, Dice, Hausdorff distance; PNGs of image, label and prediction under ``save_dir``) and
+        return ``(statistics, DSC_mean)``."""
+        if checkpoint is None:
+            if not self._save_dir:
+                raise FileNotFoundError("inference(): no checkpoint given and the trainer has no save_dir")
+            path = os.path.join(self._save_dir, "best.pth")
+        elif os.path.isfile(checkpoint):
+            if os.path.splitext(str(checkpoint))[1] != ".pth":
+                raise FileNotFoundError(checkpoint)
+            path = str(checkpoint)
+        elif os.path.isdir(checkpoint):
+            path = os.path.join(str(checkpoint), "best.pth")
+        else:
+            raise FileNotFoundError(checkpoint)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(path)
+        if self._test_loader is None:
+            raise RuntimeError("inference() runs over the test loader: the trainer was built without one")
+        if not self._save_dir:
+            raise RuntimeError("inference() writes its PNGs under save_dir: the trainer was built without one")
+        self._model.to(self._device)
+        self._model.load_state_dict(torch.load(path, map_location="cpu")["_model"])
+        evaler = InferenceEpocher(model=self._model, loader=self._test_loader, sup_criterion=self._criterion,
+                                  cur_epoch=self._cur_epoch, device=self._device)
+        evaler.init(save_dir=self._save_dir)
+        result = evaler.run()
+        return result, evaler.get_score()
 
     def state_dict(self):
         return {"_model": self._model.state_dict(), "_optimizer": self._optimizer.state_dict(),
