@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 16
+#define SPCL_ABI_VERSION 17
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -629,6 +629,39 @@ int spcl_radam_step_scaled(float* param, const float* grad, double grad_scale, f
 int spcl_radam_apply_staged(float* param, const float* grad, double grad_scale, float* exp_avg, float* exp_avg_sq, size_t n,
                             int64_t* step, const float* coef, double beta1, double beta2, double eps, double weight_decay,
                             int k, const void* const* src, void* const* dst, const float* count, void* stream);
+
+/* The other optimizers a configuration may name (contrastyou/trainer/base.py:60-69 builds optim.__dict__[config["Optim"]["name"]]:
+ * Adam, AdamW and SGD are as legal as RAdam), built like the RAdam step above: ONE flat fp32 parameter, step (int64) and lr
+ * (float) in device memory, coef = 4 floats of device scratch, grad_scale in (0, 1] applied as the gradient streams
+ * (grad_scale == 1: bit-identical to not scaling), the k <= 8 meter updates of spcl_accumulate_scalars in the same launches.
+ *
+ * Adam / AdamW (torch.optim.Adam / AdamW, single-tensor path, amsgrad = maximize = false):
+ *   decoupled == 0:  g' = grad_scale g + wd p;      decoupled == 1:  p *= (1 - lr wd),  g' = grad_scale g;
+ *   m = lerp(m, g', 1-b1);  v = b2 v + (1-b2) g'^2;  t = ++step;  p -= (lr / (1-b1^t)) m / (sqrt(v) / sqrt(1-b2^t) + eps).
+ * 28 bytes per element.  spcl_adam_step_scaled: a one-wave coefficient launch (advances *step, reads *lr, writes coef, performs
+ * the meter updates), then the streaming launch.  spcl_adam_apply_staged: NO coefficient launch -- coef[0..3] =
+ * { lr / (1-b1^t), sqrt(1-b2^t), (float)(1 - lr wd), t } were computed by the caller on the host (in double, powers by
+ * repeated squaring, lr as the float the device holds: the bits of the coefficient launch) and are already in device memory;
+ * the launch records t in *step and performs the meter updates. */
+int spcl_adam_step_scaled(float* param, const float* grad, double grad_scale, float* exp_avg, float* exp_avg_sq, size_t n,
+                          int64_t* step, const float* lr, double beta1, double beta2, double eps, double weight_decay,
+                          int decoupled, float* coef, int k, const void* const* src, void* const* dst, const float* count,
+                          void* stream);
+int spcl_adam_apply_staged(float* param, const float* grad, double grad_scale, float* exp_avg, float* exp_avg_sq, size_t n,
+                           int64_t* step, const float* coef, double beta1, double beta2, double eps, double weight_decay,
+                           int decoupled, int k, const void* const* src, void* const* dst, const float* count, void* stream);
+/* SGD (torch.optim.SGD; contrastyou/trainer/base.py:60-69 as above):  g' = grad_scale g + wd p;  with momentum != 0:
+ *   buf = g' at t == 1, buf = momentum buf + (1 - dampening) g' afterwards;  g' = nesterov ? g' + momentum buf : buf;
+ *   p -= lr g'.   Whether a step is the first is read from DEVICE memory (the counter the coefficient launch advanced, or the
+ * staged coef[3]), never decided by the host: a replayed hipGraph must not repeat step 1.  momentum_buffer is NULL if and
+ * only if momentum == 0; that path moves 12 bytes per element and touches no buffer, with momentum it moves 20.
+ * coef = { lr, 0, 0, t }.  Nesterov needs momentum > 0 and dampening == 0. */
+int spcl_sgd_step_scaled(float* param, const float* grad, double grad_scale, float* momentum_buffer, size_t n, int64_t* step,
+                         const float* lr, double momentum, double dampening, double weight_decay, int nesterov, float* coef,
+                         int k, const void* const* src, void* const* dst, const float* count, void* stream);
+int spcl_sgd_apply_staged(float* param, const float* grad, double grad_scale, float* momentum_buffer, size_t n, int64_t* step,
+                          const float* coef, double momentum, double dampening, double weight_decay, int nesterov, int k,
+                          const void* const* src, void* const* dst, const float* count, void* stream);
 
 /* Running means of the host-side meters (contrastyou/meters/averagemeter.py via MeterInterface) kept on the device:
  * for i < k (k <= 8):  dst[i][0] += count[i] * src[i][0];  dst[i][1] += count[i].  src / dst / count are HOST arrays

@@ -3,6 +3,7 @@
 // torch's foreach implementation is ~40 elementwise launches over the 1.3 M-element flat parameter (~270 us per
 // step); this is one 1-thread "tick" (step counter + the scalar coefficients, in double) and one streaming kernel
 // (p, g, m, v read once, p, m, v written once: 28 bytes per element).
+// Adam / AdamW and SGD -- the other optimizers a configuration may name (base.py:60-69) -- follow the same recipe below.
 #include <string.h>
 #include "common.hpp"
 
@@ -100,6 +101,128 @@ __global__ __launch_bounds__(256) void radam_apply_kernel(float* __restrict__ p,
   if (blockIdx.x == 0 && threadIdx.x < (int)(n - 4 * n4)) {  // tail of n % 4 elements
     const size_t i = 4 * n4 + threadIdx.x;
     upd(p[i], g[i], m[i], v[i]);
+  }
+}
+
+// ---- Adam / AdamW and SGD (contrastyou/trainer/base.py:60-69 builds optim.__dict__[config["Optim"]["name"]]: the other names a
+// config may carry).  Same recipe as RAdam above: a one-wave tick (step counter, scalars in double, meter adds) and one
+// streaming kernel, or -- staged -- the streaming kernel alone with host-computed scalars.
+
+__device__ __forceinline__ void scalar_add(const ScalarAdds& a, int i) {
+  a.dst[i][0] = fmaf(a.count[i], a.src[i][0], a.dst[i][0]);
+  a.dst[i][1] += a.count[i];
+}
+
+// coef[0] = lr / (1 - beta1^t);  coef[1] = sqrt(1 - beta2^t);  coef[2] = (float)(1 - lr wd) (the decoupled decay's factor);
+// coef[3] = t   (torch/optim/adam.py _single_tensor_adam: step_size, bias_correction2_sqrt, param.mul_(1 - lr * weight_decay))
+__global__ __launch_bounds__(64) void adam_tick_kernel(int64_t* step, const float* lr, double beta1, double beta2, double wd,
+                                                       float* coef, ScalarAdds a) {
+#pragma clang fp contract(off)  // (IEEE operations one by one, as the host computes them: optim.py adam_coefficients)
+  if (threadIdx.x > 0) {
+    if ((int)threadIdx.x <= a.k) scalar_add(a, threadIdx.x - 1);
+    return;
+  }
+  const int64_t t = step[0] + 1;
+  step[0] = t;
+  const double l = (double)lr[0];
+  const double bc1 = 1.0 - ipow(beta1, t), bc2 = 1.0 - ipow(beta2, t);
+  coef[0] = (float)(l / bc1);
+  coef[1] = (float)sqrt(bc2);
+  coef[2] = (float)(1.0 - l * wd);
+  coef[3] = (float)t;
+}
+
+template <bool STAGED, bool DECOUPLED>
+__global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, size_t n4, size_t n,
+                                                         const float* __restrict__ coef, float omb1, float beta2, float omb2,
+                                                         float eps, float wd, float gscale, int64_t* step, ScalarAdds a) {
+  const float c_m = coef[0], c_s = coef[1], c_d = coef[2];
+  if (STAGED && blockIdx.x == 0) {
+    if (threadIdx.x == 0) step[0] = (int64_t)coef[3];
+    else if ((int)threadIdx.x <= a.k) scalar_add(a, threadIdx.x - 1);
+  }
+  auto upd = [&](float& pp, float gg, float& mm, float& vv) {
+#pragma clang fp contract(off)  // (only the fmaf written below fuse: eager and staged steps, scaled or not, round alike)
+    gg *= gscale;                              // gscale: 1 / world of the data-parallel mean (1.f: exact identity)
+    if (DECOUPLED) pp *= c_d;                  // param.mul_(1 - lr * weight_decay)
+    else gg = fmaf(wd, pp, gg);                // grad.add(param, alpha=weight_decay)
+    mm = fmaf(omb1, gg - mm, mm);              // lerp_(grad, 1 - beta1)
+    vv = fmaf(vv, beta2, omb2 * gg * gg);      // mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    pp -= (c_m * mm) / (sqrtf(vv) / c_s + eps);  // addcdiv_(exp_avg, sqrt(v) / bias_correction2_sqrt + eps, value=-step_size)
+  };
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    f32x4 pp = ((f32x4*)p)[i], gg = ((const f32x4*)g)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = pp[e], me = mm[e], ve = vv[e];
+      upd(pe, gg[e], me, ve);
+      pp[e] = pe; mm[e] = me; vv[e] = ve;
+    }
+    ((f32x4*)p)[i] = pp;
+    ((f32x4*)m)[i] = mm;
+    ((f32x4*)v)[i] = vv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n - 4 * n4)) {  // tail of n % 4 elements
+    const size_t i = 4 * n4 + threadIdx.x;
+    upd(p[i], g[i], m[i], v[i]);
+  }
+}
+
+// coef[0] = lr (the float the device holds);  coef[3] = t
+__global__ __launch_bounds__(64) void sgd_tick_kernel(int64_t* step, const float* lr, float* coef, ScalarAdds a) {
+  if (threadIdx.x > 0) {
+    if ((int)threadIdx.x <= a.k) scalar_add(a, threadIdx.x - 1);
+    return;
+  }
+  const int64_t t = step[0] + 1;
+  step[0] = t;
+  coef[0] = lr[0];
+  coef[1] = 0.f;
+  coef[2] = 0.f;
+  coef[3] = (float)t;
+}
+
+// torch/optim/sgd.py _single_tensor_sgd.  "first step" (buf = g', torch's `momentum_buffer is None`) is read from DEVICE memory
+// -- the counter the tick just advanced, or the staged coef[3] -- so that a replayed graph does not repeat step 1.
+// MOMENTUM == false: buf is never touched (12 bytes per element); true: 20, and 16 at t == 1 (buf is only written).
+template <bool STAGED, bool MOMENTUM>
+__global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ buf, size_t n4, size_t n,
+                                                        const float* __restrict__ coef, float wd, float mom, float omd,
+                                                        int nesterov, float gscale, int64_t* step, ScalarAdds a) {
+  const float lr = coef[0];
+  const bool first = MOMENTUM && (STAGED ? coef[3] == 1.f : step[0] == 1);
+  if (STAGED && blockIdx.x == 0) {
+    if (threadIdx.x == 0) step[0] = (int64_t)coef[3];
+    else if ((int)threadIdx.x <= a.k) scalar_add(a, threadIdx.x - 1);
+  }
+  auto upd = [&](float& pp, float gg, float& bb) {
+#pragma clang fp contract(off)
+    gg = fmaf(wd, pp, gg * gscale);            // grad.add(param, alpha=weight_decay);  gscale 1.f: exact identity
+    if (MOMENTUM) {
+      bb = first ? gg : fmaf(mom, bb, omd * gg);  // buf.mul_(momentum).add_(grad, alpha=1 - dampening)
+      gg = nesterov ? fmaf(mom, bb, gg) : bb;
+    }
+    pp = fmaf(-lr, gg, pp);                    // param.add_(grad, alpha=-lr)
+  };
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    f32x4 pp = ((f32x4*)p)[i], gg = ((const f32x4*)g)[i], bb = {0.f, 0.f, 0.f, 0.f};
+    if (MOMENTUM && !first) bb = ((f32x4*)buf)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = pp[e], be = bb[e];
+      upd(pe, gg[e], be);
+      pp[e] = pe; bb[e] = be;
+    }
+    ((f32x4*)p)[i] = pp;
+    if (MOMENTUM) ((f32x4*)buf)[i] = bb;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n - 4 * n4)) {  // tail of n % 4 elements
+    const size_t i = 4 * n4 + threadIdx.x;
+    float be = (MOMENTUM && !first) ? buf[i] : 0.f;
+    upd(p[i], g[i], be);
+    if (MOMENTUM) buf[i] = be;
   }
 }
 
@@ -261,5 +384,126 @@ extern "C" int spcl_radam_apply_staged(float* param, const float* grad, double g
               exp_avg_sq, n4, n, coef, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
               (float)weight_decay, (float)grad_scale, step, adds);
   SPCL_LAUNCH_CHECK("radam_apply_staged");
+  return SPCL_OK;
+}
+
+// ---- Adam / AdamW (include/spcl_hip.h: spcl_adam_step_scaled / spcl_adam_apply_staged)
+static int adam_check(const char* who, const void* param, const void* grad, double grad_scale, const void* exp_avg,
+                      const void* exp_avg_sq, size_t n, const void* step, const void* lr_or_coef, const void* coef,
+                      double beta1, double beta2, double eps, double weight_decay, int decoupled, int k,
+                      const void* const* src, void* const* dst, const float* count, ScalarAdds& adds) {
+  SPCL_CHECK_ARG(grad_scale > 0.0 && grad_scale <= 1.0, "%s: grad_scale in (0, 1]", who);
+  SPCL_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step && lr_or_coef && coef, "%s: null pointer", who);
+  SPCL_CHECK_ARG(k >= 0 && k <= 8 && (k == 0 || (src && dst && count)), "%s: 0 <= k <= 8 scalar adds", who);
+  adds.k = 0;
+  if (k > 0)
+    if (int rc = fill_scalar_adds(adds, k, src, dst, count, who)) return rc;
+  SPCL_CHECK_ARG(n > 0, "%s: empty parameter", who);
+  SPCL_CHECK_ARG(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)coef) % 16 == 0,
+                 "%s: buffers must be 16-byte aligned", who);
+  SPCL_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "%s: betas", who);
+  SPCL_CHECK_ARG(eps >= 0.0 && weight_decay >= 0.0 && (decoupled == 0 || decoupled == 1),
+                 "%s: eps, weight_decay >= 0 and decoupled in {0, 1}", who);
+  return SPCL_OK;
+}
+
+static unsigned stream_blocks(size_t n4) {
+  size_t blocks = (n4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  return (unsigned)blocks;
+}
+
+extern "C" int spcl_adam_step_scaled(float* param, const float* grad, double grad_scale, float* exp_avg, float* exp_avg_sq,
+                                     size_t n, int64_t* step, const float* lr, double beta1, double beta2, double eps,
+                                     double weight_decay, int decoupled, float* coef, int k, const void* const* src,
+                                     void* const* dst, const float* count, void* stream) {
+  ScalarAdds adds;
+  if (int rc = adam_check("adam_step", param, grad, grad_scale, exp_avg, exp_avg_sq, n, step, lr, coef, beta1, beta2, eps,
+                          weight_decay, decoupled, k, src, dst, count, adds))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  SPCL_LAUNCH(adam_tick_kernel, dim3(1), dim3(k > 0 ? 64 : 1), 0, st, step, lr, beta1, beta2, weight_decay, coef, adds);
+  const size_t n4 = n / 4;
+  auto kern = decoupled ? adam_apply_kernel<false, true> : adam_apply_kernel<false, false>;
+  SPCL_LAUNCH(kern, dim3(stream_blocks(n4)), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n4, n, (const float*)coef,
+              (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)grad_scale,
+              (int64_t*)nullptr, adds);
+  SPCL_LAUNCH_CHECK("adam_step");
+  return SPCL_OK;
+}
+
+extern "C" int spcl_adam_apply_staged(float* param, const float* grad, double grad_scale, float* exp_avg, float* exp_avg_sq,
+                                      size_t n, int64_t* step, const float* coef, double beta1, double beta2, double eps,
+                                      double weight_decay, int decoupled, int k, const void* const* src, void* const* dst,
+                                      const float* count, void* stream) {
+  ScalarAdds adds;
+  if (int rc = adam_check("adam_apply_staged", param, grad, grad_scale, exp_avg, exp_avg_sq, n, step, coef, coef, beta1,
+                          beta2, eps, weight_decay, decoupled, k, src, dst, count, adds))
+    return rc;
+  const size_t n4 = n / 4;
+  auto kern = decoupled ? adam_apply_kernel<true, true> : adam_apply_kernel<true, false>;
+  SPCL_LAUNCH(kern, dim3(stream_blocks(n4)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n4, n, coef,
+              (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)grad_scale,
+              step, adds);
+  SPCL_LAUNCH_CHECK("adam_apply_staged");
+  return SPCL_OK;
+}
+
+// ---- SGD (include/spcl_hip.h: spcl_sgd_step_scaled / spcl_sgd_apply_staged)
+static int sgd_check(const char* who, const void* param, const void* grad, double grad_scale, const void* momentum_buffer,
+                     size_t n, const void* step, const void* lr_or_coef, const void* coef, double momentum, double dampening,
+                     double weight_decay, int nesterov, int k, const void* const* src, void* const* dst, const float* count,
+                     ScalarAdds& adds) {
+  SPCL_CHECK_ARG(grad_scale > 0.0 && grad_scale <= 1.0, "%s: grad_scale in (0, 1]", who);
+  SPCL_CHECK_ARG(param && grad && step && lr_or_coef && coef, "%s: null pointer", who);
+  SPCL_CHECK_ARG(k >= 0 && k <= 8 && (k == 0 || (src && dst && count)), "%s: 0 <= k <= 8 scalar adds", who);
+  adds.k = 0;
+  if (k > 0)
+    if (int rc = fill_scalar_adds(adds, k, src, dst, count, who)) return rc;
+  SPCL_CHECK_ARG(n > 0, "%s: empty parameter", who);
+  SPCL_CHECK_ARG(momentum >= 0.0 && momentum < 1e30 && weight_decay >= 0.0 && dampening == dampening && dampening > -1e30 &&
+                     dampening < 1e30,
+                 "%s: momentum, weight_decay >= 0 and finite", who);
+  SPCL_CHECK_ARG((nesterov == 0 || nesterov == 1) && (!nesterov || (momentum > 0.0 && dampening == 0.0)),
+                 "%s: Nesterov momentum requires a momentum and zero dampening", who);
+  SPCL_CHECK_ARG((momentum_buffer != nullptr) == (momentum != 0.0),
+                 "%s: momentum_buffer must be given with a momentum and NULL without one", who);
+  SPCL_CHECK_ARG(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buffer | (uintptr_t)coef) % 16 == 0,
+                 "%s: buffers must be 16-byte aligned", who);
+  return SPCL_OK;
+}
+
+extern "C" int spcl_sgd_step_scaled(float* param, const float* grad, double grad_scale, float* momentum_buffer, size_t n,
+                                    int64_t* step, const float* lr, double momentum, double dampening, double weight_decay,
+                                    int nesterov, float* coef, int k, const void* const* src, void* const* dst,
+                                    const float* count, void* stream) {
+  ScalarAdds adds;
+  if (int rc = sgd_check("sgd_step", param, grad, grad_scale, momentum_buffer, n, step, lr, coef, momentum, dampening,
+                         weight_decay, nesterov, k, src, dst, count, adds))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  SPCL_LAUNCH(sgd_tick_kernel, dim3(1), dim3(k > 0 ? 64 : 1), 0, st, step, lr, coef, adds);
+  const size_t n4 = n / 4;
+  auto kern = momentum_buffer ? sgd_apply_kernel<false, true> : sgd_apply_kernel<false, false>;
+  SPCL_LAUNCH(kern, dim3(stream_blocks(n4)), dim3(256), 0, st, param, grad, momentum_buffer, n4, n, (const float*)coef,
+              (float)weight_decay, (float)momentum, (float)(1.0 - dampening), nesterov, (float)grad_scale, step, adds);
+  SPCL_LAUNCH_CHECK("sgd_step");
+  return SPCL_OK;
+}
+
+extern "C" int spcl_sgd_apply_staged(float* param, const float* grad, double grad_scale, float* momentum_buffer, size_t n,
+                                     int64_t* step, const float* coef, double momentum, double dampening, double weight_decay,
+                                     int nesterov, int k, const void* const* src, void* const* dst, const float* count,
+                                     void* stream) {
+  ScalarAdds adds;
+  if (int rc = sgd_check("sgd_apply_staged", param, grad, grad_scale, momentum_buffer, n, step, coef, coef, momentum,
+                         dampening, weight_decay, nesterov, k, src, dst, count, adds))
+    return rc;
+  const size_t n4 = n / 4;
+  auto kern = momentum_buffer ? sgd_apply_kernel<true, true> : sgd_apply_kernel<true, false>;
+  SPCL_LAUNCH(kern, dim3(stream_blocks(n4)), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buffer, n4, n, coef,
+              (float)weight_decay, (float)momentum, (float)(1.0 - dampening), nesterov, (float)grad_scale, step, adds);
+  SPCL_LAUNCH_CHECK("sgd_apply_staged");
   return SPCL_OK;
 }

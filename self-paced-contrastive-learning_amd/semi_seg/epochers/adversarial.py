@@ -38,9 +38,9 @@ class AdversarialEpocher(SemiSupervisedEpocher):
         self._reg_weight = float(reg_weight)
         self._dis_consider_image = dis_consider_image
         self._discr_flat = discr_flat_params
-        from ...optim import FusedRAdam
+        from ...optim import is_fused
         if discr_flat_params is not None:
-            discr_flat_params.fold_mean = isinstance(discr_optimizer, FusedRAdam)
+            discr_flat_params.fold_mean = is_fused(discr_optimizer)
         self._unlabeled_iter = None
         self._zero = None
 
@@ -86,8 +86,8 @@ class AdversarialEpocher(SemiSupervisedEpocher):
         else:
             optimizer.zero_grad(set_to_none=True)
             loss.backward(gradient=self._unit)
-        from ...optim import FusedRAdam
-        fused = isinstance(optimizer, FusedRAdam) and flat is not None
+        from ...optim import is_fused
+        fused = is_fused(optimizer) and flat is not None
         adds = None
         if self.on_master():
             _meters.begin_batch()

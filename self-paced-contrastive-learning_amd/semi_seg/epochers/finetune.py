@@ -240,12 +240,12 @@ class FineTuneEpocher(_EpocherBase):
         self._labeled_loader = labeled_loader
         self._sup_criterion = sup_criterion
         self._flat_params = flat_params
-        from ...optim import FusedRAdam
+        from ...optim import is_fused
         if flat_params is not None:
-            # FusedRAdam: the exchange leaves the ranks' SUM, 1 / world is applied inside the RAdam kernel; any other
+            # a fused optimizer (optim.is_fused): the exchange leaves the ranks' SUM, 1 / world is applied inside its kernel; any other
             # optimizer reads the bucket as it is and must find the MEAN there (the flag is state of the shared FlatParams:
             # an earlier epocher may have set it)
-            flat_params.fold_mean = isinstance(optimizer, FusedRAdam)
+            flat_params.fold_mean = is_fused(optimizer)
         self._unit = None
         # the step as a hipGraph (stepgraph.py): image and label map are copied into persistent buffers in front of the
         # replay; the Dice counts come back in persistent [B, C] tensors and are handed to the meter after it
@@ -317,8 +317,8 @@ class FineTuneEpocher(_EpocherBase):
         return sup_loss
 
     def _graph_key(self, image, target):
-        from ...optim import FusedRAdam
-        if (self._device.type != "cuda" or self._flat_params is None or not isinstance(self._optimizer, FusedRAdam)
+        from ...optim import is_fused
+        if (self._device.type != "cuda" or self._flat_params is None or not is_fused(self._optimizer)
                 or getattr(self._flat_params, "_early_idx", None) is not None):
             return None
         if self._static is not None and (self._static[0].shape != image.shape or self._static[0].dtype != image.dtype
@@ -362,8 +362,8 @@ class FineTuneEpocher(_EpocherBase):
             self._flat_params.allreduce_()
 
     def step_update(self, sup_loss):
-        from ...optim import FusedRAdam
-        if isinstance(self._optimizer, FusedRAdam) and self._flat_params is not None:
+        from ...optim import is_fused
+        if is_fused(self._optimizer) and self._flat_params is not None:
             adds = None
             if self.on_master():  # the meter's device add rides in the optimizer's coefficient launch (as in pre-training)
                 _meters.begin_batch()

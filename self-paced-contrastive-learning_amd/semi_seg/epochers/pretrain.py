@@ -55,12 +55,12 @@ class PretrainEncoderEpocher:
         self._affine_transformer = TensorRandomFlip(axis=[1, 2], threshold=0.8)
         self._grad_bucket = grad_bucket
         self._flat_params = flat_params  # optimizer steps ONE flat parameter (ddp.FlatParams) when given
-        from ...optim import FusedRAdam
+        from ...optim import is_fused
         if flat_params is not None:
-            # FusedRAdam: the exchange leaves the ranks' SUM, 1 / world is applied inside the RAdam kernel; any other
+            # a fused optimizer (optim.is_fused): the exchange leaves the ranks' SUM, 1 / world is applied inside its kernel; any other
             # optimizer reads the bucket as it is and must find the MEAN there (the flag is state of the shared FlatParams:
             # an earlier epocher may have set it)
-            flat_params.fold_mean = isinstance(optimizer, FusedRAdam)
+            flat_params.fold_mean = is_fused(optimizer)
         self._hooks = []
         self.meters = MeterInterface(default_focus=self.meter_focus)
         with self.meters.focus_on(self.meter_focus):
@@ -169,9 +169,9 @@ class PretrainEncoderEpocher:
         """everything a capture of this step bakes into its launches, or None when the step cannot be captured: images'
         shape and dtype, the batch size, and what every hook declares (``EpocherHook.graph_key``: class, weight, age
         parameter ...)."""
-        from ...optim import FusedRAdam
+        from ...optim import is_fused
         flat = self._flat_params
-        if (self._device.type != "cuda" or flat is None or not isinstance(self._optimizer, FusedRAdam)
+        if (self._device.type != "cuda" or flat is None or not is_fused(self._optimizer)
                 or (getattr(flat, "_early_idx", None) is not None and not _ddp.is_distributed()) or not self._hooks
                 or tuple(self._affine_transformer._axis) != (1, 2)):
             return None
@@ -317,8 +317,8 @@ class PretrainEncoderEpocher:
     def step_update(self, reg_loss):
         if self.on_master():
             self.meters["reg_loss"].add(reg_loss.detach())
-        from ...optim import FusedRAdam
-        if isinstance(self._optimizer, FusedRAdam):  # the meters' device adds ride in the optimizer's coefficient launch
+        from ...optim import is_fused
+        if is_fused(self._optimizer):  # the meters' device adds ride in the optimizer's coefficient launch
             scale = self._flat_params.grad_scale if self._flat_params is not None else 1.0  # (1 / world when fold_mean)
             self._optimizer.step(scalar_adds=_meters.take_batch(), grad_scale=scale, stage=self.stage)
         else:

@@ -36,9 +36,9 @@ class SemiSupervisedEpocher(_EpocherBase):
         self._affine_transformer = TensorRandomFlip(axis=[1, 2], threshold=0.8)
         self._two_stage, self._disable_bn = two_stage, disable_bn
         self._flat_params = flat_params
-        from ...optim import FusedRAdam
+        from ...optim import is_fused
         if flat_params is not None:
-            flat_params.fold_mean = isinstance(optimizer, FusedRAdam)
+            flat_params.fold_mean = is_fused(optimizer)
         self._hooks = []
         self._unit = None
         super().__init__(model=model, num_batches=num_batches, cur_epoch=cur_epoch, device=device)
@@ -174,8 +174,8 @@ class SemiSupervisedEpocher(_EpocherBase):
         return sup_loss, reg_loss
 
     def _update(self, sup_loss, reg_loss):
-        from ...optim import FusedRAdam
-        if isinstance(self._optimizer, FusedRAdam) and self._flat_params is not None:
+        from ...optim import is_fused
+        if is_fused(self._optimizer) and self._flat_params is not None:
             adds = None
             if self.on_master():  # the meters' device adds ride in the optimizer's coefficient launch
                 _meters.begin_batch()

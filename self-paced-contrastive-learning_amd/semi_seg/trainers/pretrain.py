@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from ... import ddp as _ddp
-from ...optim import FusedRAdam
+from ...optim import FusedAdam, FusedAdamW, FusedRAdam, FusedSGD
 from ..epochers.pretrain import PretrainDecoderEpocher, PretrainEncoderEpocher
 from ..hooks.creator import feature_until_from_hooks
 
@@ -78,9 +78,19 @@ def read_optim_sched(config, *, lr=None, weight_decay=None, warmup_max=None, mul
     return name, optim_cfg, sched
 
 
+_FUSED = {"Adam": FusedAdam, "AdamW": FusedAdamW, "SGD": FusedSGD}
+_TORCH_ONLY_KEYS = ("amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused")  # not implemented by the fused steps
+
+
 def build_optimizer(name, flat_param, optim_cfg):
+    """``optim.__dict__[name](...)`` of contrastyou/trainer/base.py:60-69 on the flat parameter.  RAdam, and Adam / AdamW / SGD
+    on a CUDA parameter, are the fused HIP steps (torch.optim semantics; the epochers capture the step, fold the data-parallel
+    mean and carry the meters only with these).  Any other name, a CPU parameter, or a section that switches on a torch
+    feature the fused steps do not implement (``_TORCH_ONLY_KEYS``) gets the ``torch.optim`` class."""
     if name == "RAdam":
         return FusedRAdam([flat_param], **optim_cfg)  # torch.optim.RAdam semantics, HIP kernel
+    if name in _FUSED and flat_param.is_cuda and not any(optim_cfg.get(k) for k in _TORCH_ONLY_KEYS):
+        return _FUSED[name]([flat_param], **{k: v for k, v in optim_cfg.items() if k not in _TORCH_ONLY_KEYS})
     if hasattr(torch.optim, name):
         return getattr(torch.optim, name)([flat_param], **optim_cfg)
     raise KeyError(name)
