@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 17
+#define SPCL_ABI_VERSION 18
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -589,6 +589,23 @@ size_t spcl_surface_workspace_bytes(int B, int H, int W, int n_report);
 int spcl_surface_distances(const int64_t* pred, const int64_t* target, int B, int H, int W, int C, const int* report,
                            int n_report, double sy, double sx, double percentile, double* hd, double* mhd, double* asd,
                            uint8_t* empty, void* ws, size_t ws_bytes, void* stream);
+
+/* The same metrics per SCAN (csrc/surface.hip): what SurfaceMeter._evalue (contrastyou/meters/surface_meter.py:109-128) computes
+ * when `*hw` is a volume -- medpy's n-D erosion and exact n-D distance transform under `voxelspacing`
+ * (contrastyou/meters/surface_distance.py:9-29), restated from their definition.
+ *   pred, target  [V][D][H][W] int64 class-coded maps: V volumes of D slices, axis 1 is z
+ *   per (v, r): A = (pred[v] == report[r]), T = (target[v] == report[r]);  border(m) = the voxels of m with one of their SIX
+ *   neighbours (+-x, +-y, +-z) outside m or outside the volume -- in a one-slice volume every voxel of m, which is NOT the 2-D
+ *   call's border of that slice;  squared distance of two voxels = ((dz sz)^2 + (dy sy)^2) + (dx sx)^2, rounded in that order
+ *   (exact int32 under unit spacing);  directed sets, hd, mhd (numpy's linear percentile), asd and empty as in the 2-D call
+ *   hd, mhd, asd, empty   [V][n_report]
+ * D, H, W <= 1024, D H W < 2^31, spacing finite and positive, percentile in [0, 100].  The cost is D H W (D + H + W) per pair
+ * whatever the masks look like.  ws: spcl_surface_3d_workspace_bytes(V, D, H, W, n_report) bytes, 16-byte aligned
+ * (0 = unsupported shape).  Five launches on `stream`, nothing is read back; the same input gives the same bits. */
+size_t spcl_surface_3d_workspace_bytes(int V, int D, int H, int W, int n_report);
+int spcl_surface_distances_3d(const int64_t* pred, const int64_t* target, int V, int D, int H, int W, int C, const int* report,
+                              int n_report, double sz, double sy, double sx, double percentile, double* hd, double* mhd,
+                              double* asd, uint8_t* empty, void* ws, size_t ws_bytes, void* stream);
 
 /* Decoder data movement (NHWC, CS a multiple of 16): nn.Upsample(scale_factor=2) of `_UpConv` (unet.py:89) and its
  * backward (H, W = the low-resolution size in both calls), torch.cat((skip, up), dim=1) (unet.py:194-224) and its

@@ -1,8 +1,8 @@
 """Minimal meters for the hot path (the reference's ``contrastyou/meters`` package is out of scope): the
 three meter names the InfoNCE hooks write (``loss``, ``sp_weight``, ``age_param``) plus ``reg_loss``/``lr``.
 Values may be device tensors: they are accumulated ON DEVICE and read back once, in ``summary()`` -- the reference's
-per-step ``.item()`` synchronisations (K19) disappear.  ``UniversalDice`` and ``SurfaceMeter`` (evaluation / inference)
-keep per-sample device results the same way."""
+per-step ``.item()`` synchronisations (K19) disappear.  ``UniversalDice``, ``SurfaceMeter`` and ``VolumeSurfaceMeter``
+(evaluation / inference) keep per-sample device results the same way."""
 from collections import OrderedDict
 from contextlib import contextmanager
 
@@ -333,3 +333,46 @@ class SurfaceMeter:
 
     def __repr__(self):
         return f"C={self._C}, report_axis={self._report_axis}\n\t" + "\t".join(f"{k}:{v}" for k, v in self.summary().items())
+
+
+class VolumeSurfaceMeter(SurfaceMeter):
+    """``SurfaceMeter`` per SCAN: the value ``surface_meter.py:109-128`` computes when its ``*hw`` is a volume (medpy's n-D
+    erosion and distance transform under ``voxelspacing``), one row per scan and reported class, mean / std over the
+    recorded scans, ``summary()`` with ``HD3D{i}`` / ``MHD3D{i}`` / ``ASD3D{i}``.
+
+    ``add(pred, target, voxelspacing)`` takes ONE scan per call, class-coded integer ``[D,H,W]`` or ``[D,1,H,W]`` (a 4-D
+    input is never a simplex here), axis 0 = z in the order given, ``voxelspacing`` = None, one float or ``(sz, sy, sx)``.
+    It is one HIP call (``functional.surface_distances_3d``) whose values and flags stay on the device.  A volume holds
+    every class unless the prediction misses it altogether -- the slice-wise meter drops a scan as soon as one slice lacks
+    one class --; a scan in which a reported class is missing from the whole of ``pred`` or ``target`` is left out of
+    ``value()`` and counted by ``skipped_scans``, ``raise_on_empty=True`` raises the reference's ``RuntimeError`` instead."""
+    abbr = {"mod_hausdorff": "MHD3D", "hausdorff": "HD3D", "average_surface": "ASD3D"}
+
+    def add(self, pred, target, voxelspacing=None, raise_on_empty=False):
+        from .. import functional as F_hip
+        assert pred.shape == target.shape, \
+            f"incompatible shape of `pred` and `target`, given {pred.shape} and {target.shape}."
+        assert not pred.requires_grad and not target.requires_grad
+        if pred.is_floating_point() or target.is_floating_point():
+            raise TypeError(f"VolumeSurfaceMeter takes class-coded integer maps, given {pred.dtype} and {target.dtype}")
+        if pred.dim() == 4 and pred.shape[1] == 1:
+            pred, target = pred.squeeze(1), target.squeeze(1)
+        if pred.dim() != 3:
+            raise TypeError(f"VolumeSurfaceMeter takes one scan, [D,H,W] or [D,1,H,W], given {tuple(pred.shape)}")
+        self.add_distances(*F_hip.surface_distances_3d(pred, target, self._C, self._report_axis, voxelspacing, 95.0),
+                           raise_on_empty=raise_on_empty)
+
+    def add_distances(self, hd, mhd, asd, empty, raise_on_empty=False):
+        """record one scan's [1, n_report] results of ``functional.surface_distances_3d`` (device tensors the caller hands
+        over: several meters of one pass share one call)"""
+        assert hd.shape == empty.shape == (1, len(self._report_axis)), (hd.shape, empty.shape)
+        if raise_on_empty and bool(empty.any()):
+            raise RuntimeError("The first or the second supplied array does not contain any binary object.")
+        self._values.append({"hd": hd, "mhd": mhd, "asd": asd}[self.meter_choices[self._surface_name]])
+        self._empty.append(empty)
+        self._n += 1
+
+    @property
+    def skipped_scans(self):
+        """how many recorded scans lack a reported class and are left out of ``value()`` (reads the flags back)"""
+        return self.skipped_batches

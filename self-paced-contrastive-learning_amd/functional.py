@@ -2457,6 +2457,48 @@ def surface_distances(pred: torch.Tensor, target: torch.Tensor, C: int, report_a
     return vals[0], vals[1], vals[2], empty
 
 
+_SURFACE3D_WS = {}  # (device, V, D, H, W, n_report) -> workspace, reused as _SURFACE_WS is
+
+
+def surface_distances_3d(pred: torch.Tensor, target: torch.Tensor, C: int, report_axis=None, voxelspacing=None,
+                         percentile: float = 95.0):
+    """``surface_distances`` per VOLUME (``spcl_surface_distances_3d``): class-coded integer ``[D,H,W]`` (one volume) or
+    ``[V,D,H,W]`` maps, 6-neighbour borders, exact 3-D Euclidean distances -> ``(hd, mhd, asd, empty)``, float64 / uint8
+    ``[V, n_report]``.  ``voxelspacing``: None (1, 1, 1), one float for the three axes, or ``(sz, sy, sx)``.  Everything
+    stays on the device."""
+    if pred.shape != target.shape:
+        raise AssertionError(f"incompatible shape of `pred` and `target`, given {pred.shape} and {target.shape}.")
+    if pred.dim() not in (3, 4) or pred.is_floating_point() or target.is_floating_point():
+        raise TypeError("surface_distances_3d takes class-coded integer [D,H,W] or [V,D,H,W] maps, given "
+                        f"{tuple(pred.shape)} {pred.dtype}")
+    _n.require_gpu(pred, target)
+    report = list(range(C)) if report_axis is None else [int(c) for c in report_axis]
+    if voxelspacing is None:
+        sz = sy = sx = 1.0
+    elif isinstance(voxelspacing, (int, float)):
+        sz = sy = sx = float(voxelspacing)
+    else:
+        sz, sy, sx = (float(v) for v in voxelspacing)
+    p, t = pred.detach().long().contiguous(), target.detach().long().contiguous()
+    if p.dim() == 3:
+        p, t = p.unsqueeze(0), t.unsqueeze(0)
+    V, D, H, W = p.shape
+    R, dev = len(report), p.device
+    key = (dev, V, D, H, W, R)
+    ws = _SURFACE3D_WS.get(key)
+    if ws is None:
+        nbytes = _n.call("spcl_surface_3d_workspace_bytes", V, D, H, W, R)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None  # (0: the call below says why)
+        if ws is not None:
+            _SURFACE3D_WS[key] = ws
+    vals = torch.empty((3, V, R), dtype=torch.float64, device=dev)
+    empty = torch.empty((V, R), dtype=torch.uint8, device=dev)
+    _n.call("spcl_surface_distances_3d", _n.ptr(p), _n.ptr(t), V, D, H, W, int(C), (c_int * max(R, 1))(*report), R, sz, sy, sx,
+            float(percentile), _n.ptr(vals[0]), _n.ptr(vals[1]), _n.ptr(vals[2]), _n.ptr(empty), _n.ptr(ws),
+            ws.numel() if ws is not None else 0, _n.stream())
+    return vals[0], vals[1], vals[2], empty
+
+
 class _Upsample2xFn(torch.autograd.Function):
     """nn.Upsample(scale_factor=2) (nearest) of ``_UpConv`` on NHWC storage; backward = 2x2 sum."""
 

@@ -15,7 +15,7 @@ from ... import native as _n
 from ... import stepgraph as _sg
 from ...contrastyou.losses.kl import KL_div, class2one_hot
 from ...contrastyou import meters as _meters
-from ...contrastyou.meters import AverageValueMeter, MeterInterface, SurfaceMeter, UniversalDice
+from ...contrastyou.meters import AverageValueMeter, MeterInterface, SurfaceMeter, UniversalDice, VolumeSurfaceMeter
 
 _FUSED_SUP_LOSS = os.environ.get("SPCL_FUSED_SUP_LOSS", "1") != "0"  # A/B switch: 0 = the seven separate launches
 
@@ -202,7 +202,21 @@ class InferenceEpocher(EvalEpocher):
     ``save_dir/{img,gt,pred}/<file_path>.png`` (image x 255, label map, arg-max map).  The PNG writes make the pass
     host-bound, so every batch is issued eagerly instead of through the validation hipGraphs.  A batch in which a
     foreground class is missing from a slice does not count towards ``hd`` (the reference ignores the meter's
-    ``RuntimeError`` there)."""
+    ``RuntimeError`` there).
+
+    ``volumetric=True`` (off by default: meters, keys and values are then unchanged) additionally registers ``hd3d``,
+    ``mhd3d`` and ``asd3d``, three ``VolumeSurfaceMeter`` of the foreground classes fed by ONE
+    ``functional.surface_distances_3d`` call per batch with ``voxelspacing`` (None, one float or ``(sz, sy, sx)``).  Each
+    batch is taken as one volume, its slices in batch order along z: the validation loaders hand over one scan per batch
+    (``ScanBatchSampler``) and the stores list a scan's slices in file-name order, which is z order for the reference's
+    zero-padded slice names.  A batch that mixes scan names is not a volume and raises ``ValueError``."""
+    VOLUME_METERS = (("hd3d", "hausdorff"), ("mhd3d", "mod_hausdorff"), ("asd3d", "average_surface"))
+
+    def __init__(self, *, model: nn.Module, loader: Iterable, sup_criterion, cur_epoch=0, device="cuda",
+                 graph: Optional[bool] = None, volumetric: bool = False, voxelspacing=None):
+        self._volumetric, self._voxelspacing = bool(volumetric), voxelspacing  # (configure_meters runs inside __init__)
+        super().__init__(model=model, loader=loader, sup_criterion=sup_criterion, cur_epoch=cur_epoch, device=device,
+                         graph=graph)
 
     def init(self, *, save_dir: str):
         self._save_dir = str(save_dir)
@@ -211,6 +225,9 @@ class InferenceEpocher(EvalEpocher):
         meters = super().configure_meters(meters)
         C = self.num_classes
         meters.register_meter("hd", SurfaceMeter(C=C, report_axises=list(range(1, C)), metername="hausdorff"))
+        if self._volumetric:
+            for name, metername in self.VOLUME_METERS:
+                meters.register_meter(name, VolumeSurfaceMeter(C=C, report_axises=list(range(1, C)), metername=metername))
         return meters
 
     @torch.no_grad()
@@ -221,6 +238,8 @@ class InferenceEpocher(EvalEpocher):
         assert self._model.training is False, self._model.training
         for self.cur_batch_num, eval_data in zip(range(self._num_batches), self._loader):
             eval_img, eval_target, file_path, _, group = unzip_single_transformed(eval_data, self._device)
+            if self._volumetric and len(set(group)) != 1:
+                raise ValueError(f"InferenceEpocher(volumetric=True): a batch is one scan, this one mixes {sorted(set(group))}")
             eval_loss, inter, union, prediction = self._batch_with_prediction(eval_img, eval_target)
             write_img_target(eval_img, eval_target, self._save_dir, file_path)
             write_predict(prediction, self._save_dir, file_path)
@@ -228,6 +247,11 @@ class InferenceEpocher(EvalEpocher):
             dice = self.meters["dice"]
             dice.add_counts(inter, union, dice.group_names_for(inter.shape[0], list(group)))
             self.meters["hd"].add(prediction, eval_target.squeeze(1))
+            if self._volumetric:
+                distances = F_hip.surface_distances_3d(prediction, eval_target.squeeze(1), self.num_classes,
+                                                       list(range(1, self.num_classes)), self._voxelspacing, 95.0)
+                for name, _ in self.VOLUME_METERS:
+                    self.meters[name].add_distances(*distances)
 
 
 class FineTuneEpocher(_EpocherBase):

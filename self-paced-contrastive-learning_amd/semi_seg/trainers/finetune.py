@@ -117,11 +117,13 @@ class FineTuneTrainer:
             _sg.gc_release()  # (the epochers' captures keep the collector's heap frozen from one epoch to the next)
         return self.history
 
-    def inference(self, checkpoint=None):
+    def inference(self, checkpoint=None, *, volumetric=False, voxelspacing=None):
         """``Trainer.inference`` (semi_seg/trainers/base.py:127-148): load the model of a checkpoint -- ``None``: this
         trainer's ``save_dir/best.pth``; a ``.pth`` file; or a directory holding a ``best.pth`` --, run ``InferenceEpocher``
         over the test loader (loss, Dice, Hausdorff distance; PNGs of image, label and prediction under ``save_dir``) and
-        return ``(statistics, DSC_mean)``."""
+        return ``(statistics, DSC_mean)``.  ``volumetric=True`` adds the per-scan 3-D surface distances ``hd3d`` / ``mhd3d`` /
+        ``asd3d`` under ``voxelspacing`` = ``(sz, sy, sx)``: every test batch must then be one scan, slices in z order (the
+        stores list a scan's slices in file-name order, which is z order for the reference's zero-padded names)."""
         if checkpoint is None:
             if not self._save_dir:
                 raise FileNotFoundError("inference(): no checkpoint given and the trainer has no save_dir")
@@ -143,7 +145,8 @@ class FineTuneTrainer:
         self._model.to(self._device)
         self._model.load_state_dict(torch.load(path, map_location="cpu")["_model"])
         evaler = InferenceEpocher(model=self._model, loader=self._test_loader, sup_criterion=self._criterion,
-                                  cur_epoch=self._cur_epoch, device=self._device)
+                                  cur_epoch=self._cur_epoch, device=self._device, volumetric=volumetric,
+                                  voxelspacing=voxelspacing)
         evaler.init(save_dir=self._save_dir)
         result = evaler.run()
         return result, evaler.get_score()
