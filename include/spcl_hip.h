@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 18
+#define SPCL_ABI_VERSION 19
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -244,10 +244,38 @@ int spcl_conv3x3_forward(const void* x, int dtype, int N, int H, int W, int CinS
  * convolution (spcl_bnrelu_backward_rows_image3): acorr_rows [rows][64] f32, one row per 14 x 14 tile, same layout and
  * meaning per row (45 upper-triangle sums R[t'][t] + 9 image sums over the tile's pixels), so spcl_conv16_bwd_fused's
  * fold and the image3 final kernels take them unchanged.  _rows: the number of rows, 0 where the specialised kernel does
- * not take the shape (bf16, CinS == 1, CoutS == 16, H and W multiples of 14 above 112). */
+ * not take the shape (bf16, CinS == 1, CoutS == 16, H and W multiples of 14 above 112): where the library's own dispatch
+ * runs it.  The call itself takes every whole-tile size (H and W multiples of 14): spcl_block1_kernels_take answers for the
+ * call.
+ * y == NULL: the statistics-only form -- stats and acorr_rows bit for bit as with y, no output stream (32 of the launch's 36
+ * bytes per pixel); the raw output is then formed again, per tile and bit for bit, by the two launches that read it:
+ * spcl_conv3x3_forward_from_image and spcl_conv16_bwd_fused_image. */
 int spcl_conv3x3_forward_image_acorr_rows(int dtype, int N, int H, int W, int CinS, int CoutS);
 int spcl_conv3x3_forward_image_acorr(const void* x, int dtype, int N, int H, int W, int CinS, int CoutS,
                                      const void* w_packed, void* y, float* stats, float* acorr_rows, void* stream);
+/* The image block WITHOUT the first convolution's raw output (unet.py:123 -> :72-75 of the reference: Conv2d(1, 16) ->
+ * BatchNorm2d -> ReLU -> Conv2d(16, 16); the tensor between the two convolutions is 103 MB at 64 x 224^2 and was written once
+ * and read twice per step).  spcl_conv3x3_forward_from_image is the second convolution (what spcl_conv3x3_forward(in_mode 1,
+ * in_scale, in_shift) computes from the stored tensor, replacing unet.py:72-75's BatchNorm2d / ReLU / Conv2d reads of it): per
+ * 14 x 14 tile it forms the first convolution's output on the 16 x 16 halo from the f32 image [N][H][W] and
+ * w_packed_image (spcl_conv_pack_weights kind 0 of the [16][1][3][3] filters) with the instruction, operand packing and
+ * rounding of spcl_conv3x3_forward_image_acorr -- the same bits -- then applies relu(in_scale y + in_shift), zero outside the
+ * image.  y [N][H][W][16] bf16 and stats (one row set per 14 x 14 tile) as spcl_conv3x3_forward.  bf16, H and W multiples of
+ * 14.  y_image != NULL: the stored tensor is read instead (image / w_packed_image unused), on the same tiles -- the comparison
+ * form.  spcl_block1_recompute_supported: 1 where the library offers the block without the tensor, i.e. where all of its
+ * three launches have their kernel (the statistics-only spcl_conv3x3_forward_image_acorr, this call on 14-row tiles,
+ * spcl_conv16_bwd_fused_image): bf16, CinS == 1, CoutS == 16, H and W multiples of 14 above 112.  It answers for the kernels:
+ * this call writes its statistics as per-tile rows only, so a caller whose second BatchNorm goes through an accumulator
+ * block (spcl_conv_bn_acc_supported says yes: at most 4 096 tiles, e.g. N <= 16 at 224^2) keeps the stored tensor.
+ * spcl_block1_kernels_take: 1 where the block's 14 x 14-tile kernels accept a CALL whatever tile the library's own dispatch
+ * picks for the size -- this call, spcl_conv3x3_forward_image_acorr, spcl_conv16_bwd_fused and spcl_conv16_bwd_fused_image:
+ * bf16, CinS == 1, CoutS == 16, H and W multiples of 14 (the _rows / _supported queries of those calls say where the
+ * library itself uses them; this one says where they may be called). */
+int spcl_block1_recompute_supported(int dtype, int N, int H, int W, int CinS, int CoutS);
+int spcl_block1_kernels_take(int dtype, int N, int H, int W, int CinS, int CoutS);
+int spcl_conv3x3_forward_from_image(const float* image, const void* y_image, int dtype, int N, int H, int W, int CoutS,
+                                    const void* w_packed_image, const float* in_scale, const float* in_shift,
+                                    const void* w_packed, void* y, float* stats, void* stream);
 /* The decoder's torch.cat((skip, up), dim=1) -> Conv2d(2 Chalf, Cout, 3, 1, 1) (unet.py:194-197, 201-204, ... the first
  * convolution of every Up_conv block) WITHOUT the concatenated tensor: input channels [0, Chalf) are read from xa, [Chalf,
  * 2 Chalf) from xb, both dense [N][H][W][Chalf] bf16; w_packed = spcl_conv_pack_weights(kind 0) of the [Cout][2 Chalf]
@@ -477,7 +505,8 @@ int spcl_conv3x3_dgrad_bnstats_image(const void* dy, int dtype, int N, int H, in
  * weight gradient (what spcl_conv3x3_wgrad(x = y2, in_mode 1, scale2, shift2) computes; partial = the split slabs,
  * spcl_conv16_bwd_fused_splits(N, H, W) x 9 x 256 floats; the final sum goes to dw_oihw [Cout][Cin][3][3] or to a captured
  * tail, as there) AND the rows11 of spcl_conv3x3_dgrad_bnstats_image(g == NULL).  Nothing is written per pixel.
- * Same gate as spcl_conv_dgrad_bnstats_image_supported.
+ * Same gate as spcl_conv_dgrad_bnstats_image_supported (where the library's own dispatch runs it; the call also takes every
+ * image whose H and W are multiples of 14: spcl_block1_kernels_take).
  * Exactly one of rows11 ([tiles][11][CoutS], as above) / wg_rows: ONE row set per workgroup (its tiles summed in
  * registers), [11][16][spcl_conv16_bwd_fused_splits] -- the layout spcl_bnrelu_backward_wgrows_image3 finishes from without
  * a folding launch; with wg_rows the same launch folds the autocorrelation's partial rows acorr [nacorr][64] to
@@ -488,6 +517,15 @@ int spcl_conv16_bwd_fused(const void* dy, int dtype, int N, int H, int W, const 
                           const float* scale2, const float* shift2, const float* mean2, const float* image,
                           float* rows11, float* partial, float* dw_oihw, int Cin, int Cout, float* wg_rows,
                           const float* acorr, int nacorr, float* acorr16, void* stream);
+/* spcl_conv16_bwd_fused for a first conv whose raw output y2 was never stored (the backward of unet.py:75 and of the
+ * BatchNorm2d / ReLU of unet.py:73-74 in front of it): y2 is formed per tile from `image` and w_packed_image (kind 0 of the
+ * [16][1][3][3] filters), bit for bit what spcl_conv3x3_forward_image_acorr stores; every output as spcl_conv16_bwd_fused.
+ * bf16, H and W multiples of 14 (spcl_conv16_bwd_fused_image_supported). */
+int spcl_conv16_bwd_fused_image_supported(int dtype, int N, int H, int W, int CinK, int CoutS);
+int spcl_conv16_bwd_fused_image(const void* dy, int dtype, int N, int H, int W, const void* w_packed_dgrad,
+                                const void* w_packed_image, const float* scale2, const float* shift2, const float* mean2,
+                                const float* image, float* rows11, float* partial, float* dw_oihw, int Cin, int Cout,
+                                float* wg_rows, const float* acorr, int nacorr, float* acorr16, void* stream);
 int spcl_bnrelu_backward_wgrows_image3(const float* wg_rows, int nwg, const float* acorr, int nacorr, const float* w_oihw,
                                        int N, int H, int W, int C, int CS, const float* mean, const float* invstd,
                                        const float* scale, int training, float* ws, float* dgamma, float* dbeta,

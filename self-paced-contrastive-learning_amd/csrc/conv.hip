@@ -1246,20 +1246,33 @@ extern "C" int spcl_conv3x3_forward_image_acorr_rows(int dtype, int N, int H, in
   return N * cdiv(H, 14) * cdiv(W, 14);
 }
 
+// (the kernel itself takes whole 14 x 14 tiles of ANY image size: _rows says where the library's own dispatch runs it -- above
+// 112 rows, where every layer of the block is on 14-row tiles -- the call also takes the smaller whole-tile sizes, and
+// spcl_block1_kernels_take is the query that says yes exactly where the call does)
+// y == NULL: the statistics-only form (conv3x3_image_kernel<.., STORE = false>): same rows, no output stream -- the block's
+// other two launches form the output again per tile (spcl_conv3x3_forward_from_image, spcl_conv16_bwd_fused_image).
+static bool image_acorr_kernel_takes(ConvArgs& a, int dtype, int N, int H, int W, int CinS, int CoutS) {
+  if (image_acorr_args(a, dtype, N, H, W, CinS, CoutS)) return true;
+  if (!spcl_block1_kernels_take(dtype, N, H, W, CinS, CoutS)) return false;
+  a.N = N; a.H = H; a.W = W; a.CinS = CinS; a.CinK = 16; a.CoutS = CoutS; a.in_mode = 2;
+  a.tilesX = a.tilesY = 0; a.tpw = 1; a.dbg = 0;
+  return true;
+}
+
 extern "C" int spcl_conv3x3_forward_image_acorr(const void* x, int dtype, int N, int H, int W, int CinS, int CoutS,
                                                 const void* w_packed, void* y, float* stats, float* acorr_rows,
                                                 void* stream) {
-  SPCL_CHECK_ARG(x && y && w_packed && acorr_rows, "conv3x3_forward_image_acorr: null pointer");
+  SPCL_CHECK_ARG(x && w_packed && acorr_rows, "conv3x3_forward_image_acorr: null pointer");
   ConvArgs a;
   a.x = x; a.y = y; a.wp = w_packed; a.stats = stats; a.in_scale = a.in_shift = nullptr;
-  if (!image_acorr_args(a, dtype, N, H, W, CinS, CoutS)) {
-    set_error("conv3x3_forward_image_acorr: unsupported configuration (ask spcl_conv3x3_forward_image_acorr_rows)");
+  if (!image_acorr_kernel_takes(a, dtype, N, H, W, CinS, CoutS)) {
+    set_error("conv3x3_forward_image_acorr: unsupported configuration (bf16, one input channel, 16 outputs, whole 14 x 14 tiles)");
     return SPCL_EUNSUPPORTED;
   }
   a.acorr_rows = acorr_rows;
   {
     const double px = (double)N * H * W;
-    prof_cost(px * (4.0 + CoutS * 2.0) + 9.0 * 16 * CoutS * 2.0 + (double)N * cdiv(H, 14) * cdiv(W, 14) * 256.0,
+    prof_cost(px * (4.0 + (y != nullptr ? CoutS * 2.0 : 0.0)) + 9.0 * 16 * CoutS * 2.0 + (double)N * cdiv(H, 14) * cdiv(W, 14) * 256.0,
               2.0 * px * 9.0 * CinS * CoutS + 2.0 * px * 2.0 * 256.0);
   }
   if (!launch_conv_fast(a, 14, (hipStream_t)stream)) {
@@ -1267,6 +1280,75 @@ extern "C" int spcl_conv3x3_forward_image_acorr(const void* x, int dtype, int N,
     return SPCL_EUNSUPPORTED;
   }
   SPCL_LAUNCH_CHECK("conv3x3_forward_image_acorr");
+  return SPCL_OK;
+}
+
+// The image block's SECOND convolution (unet.py:75 behind :72-74, 16 -> 16 channels) reading the IMAGE: its input
+// relu(scale y1a + shift) is formed per tile from y1a = conv(image, w_packed_image), the first convolution's raw output
+// (unet.py:123), which then need not exist in memory (conv_fast.hip conv3x3_fast_kernel MODE 8) -- bit for bit what in_mode 1
+// of spcl_conv3x3_forward reads from the tensor spcl_conv3x3_forward_image_acorr stores, on the same 14 x 14 tiles.
+// y_image != NULL: that stored tensor is read instead (the same kernel's in_mode 1 form on the same tiles: the comparison).
+// spcl_block1_recompute_supported: where the library offers the block without the tensor -- all three launches at once:
+// the statistics-only image kernel with the autocorrelation rows, this one as conv3x3_fast<16, 14, 1, ., 1>, and the backward
+// as conv16_bwd_rows (spcl_conv16_bwd_fused_image).
+static bool from_image_args(ConvArgs& a, int dtype, int N, int H, int W, int CoutS) {
+  if (!spcl_block1_kernels_take(dtype, N, H, W, 1, CoutS)) return false;
+  a.N = N; a.H = H; a.W = W; a.CinS = 16; a.CinK = 16; a.CoutS = 16; a.in_mode = 1;
+  a.tilesX = a.tilesY = 0; a.tpw = 1; a.dbg = 0;
+  return true;
+}
+
+// spcl_block1_kernels_take: where the image block's 14 x 14-tile kernels accept a CALL, whatever tile the library's own
+// dispatch would pick for the size -- spcl_conv3x3_forward_image_acorr (either form), spcl_conv3x3_forward_from_image (either
+// form), spcl_conv16_bwd_fused and spcl_conv16_bwd_fused_image: bf16, one input channel, 16 outputs, H and W multiples of 14
+// (the lab switches that take the specialised kernels away take this away too).
+extern "C" int spcl_block1_kernels_take(int dtype, int N, int H, int W, int CinS, int CoutS) {
+  static const bool off = lab_env("SPCL_ACORR_IN_CONV", 1) == 0 || lab_env("SPCL_CONV_NO_FAST", 0) != 0;
+  if (off || dtype != SPCL_BF16 || N <= 0 || H < 14 || W < 14 || H % 14 || W % 14 || CinS != 1 || CoutS != 16) return 0;
+  return spcl_conv16_bwd_fused_image_supported(dtype, N, H, W, 16, 16);
+}
+
+// spcl_block1_recompute_supported answers for the KERNELS.  The caller must also be on the rows form of both BatchNorms:
+// where Conv1.b's statistics go through an accumulator block (spcl_conv_bn_acc_supported: at most 4 096 tiles, N <= 16 at
+// 224^2) MODE 8 is not offered and functional._ConvBlockFn keeps the stored tensor.
+extern "C" int spcl_block1_recompute_supported(int dtype, int N, int H, int W, int CinS, int CoutS) {
+  static const int no_fast = lab_env("SPCL_CONV_NO_FAST", 0);
+  if (no_fast || CinS != 1 || CoutS != 16) return 0;
+  if (spcl_conv3x3_forward_image_acorr_rows(dtype, N, H, W, CinS, CoutS) <= 0) return 0;
+  if (!spcl_conv16_bwd_fused_supported(dtype, N, H, W, 16, 16) || !spcl_conv16_bwd_fused_image_supported(dtype, N, H, W, 16, 16))
+    return 0;
+  ConvArgs a;
+  float dummy = 0.f;
+  a.x = nullptr; a.y = nullptr; a.wp = nullptr; a.stats = nullptr; a.in_scale = a.in_shift = nullptr;
+  if (!from_image_args(a, dtype, N, H, W, CoutS) || conv_use_gemm(16, 16, H, W)) return 0;
+  a.img1 = &dummy;
+  const TileCfg t = pick_tile_k(H, W, 16, 16);
+  return (t.tw == 14 && t.th == 14 && launch_conv_fast(a, 14, nullptr, true)) ? 1 : 0;
+}
+
+extern "C" int spcl_conv3x3_forward_from_image(const float* image, const void* y_image, int dtype, int N, int H, int W,
+                                               int CoutS, const void* w_packed_image, const float* in_scale,
+                                               const float* in_shift, const void* w_packed, void* y, float* stats,
+                                               void* stream) {
+  SPCL_CHECK_ARG((image && w_packed_image) || y_image, "conv3x3_forward_from_image: null pointer");
+  SPCL_CHECK_ARG(in_scale && in_shift && w_packed && y, "conv3x3_forward_from_image: null pointer");
+  ConvArgs a;
+  a.x = y_image; a.y = y; a.wp = w_packed; a.stats = stats; a.in_scale = in_scale; a.in_shift = in_shift;
+  if (!from_image_args(a, dtype, N, H, W, CoutS)) {
+    set_error("conv3x3_forward_from_image: unsupported configuration (bf16, 16 -> 16 channels, whole 14 x 14 tiles)");
+    return SPCL_EUNSUPPORTED;
+  }
+  if (y_image == nullptr) { a.img1 = image; a.wp1 = w_packed_image; }
+  {  // the image once (its halo re-reads hit the cache), y once, both filter sets
+    const double px = (double)N * H * W;
+    prof_cost(px * ((y_image != nullptr ? 32.0 : 4.0) + 32.0) + 2.0 * 9.0 * 16 * 16 * 2.0,
+              2.0 * px * 9.0 * 16 * 16 + (y_image != nullptr ? 0.0 : 2.0 * px * 9.0 * 16));
+  }
+  if (!launch_conv_fast(a, 14, (hipStream_t)stream)) {
+    set_error("conv3x3_forward_from_image: no kernel for N=%d H=%d W=%d", N, H, W);
+    return SPCL_EUNSUPPORTED;
+  }
+  SPCL_LAUNCH_CHECK("conv3x3_forward_from_image");
   return SPCL_OK;
 }
 

@@ -37,7 +37,8 @@ namespace spcl {
 struct Bwd16Args {
   const unsigned char* dy;  // [N][H][W][16] bf16
   const u32x4* wp;          // packed dgrad fragments of the 16 -> 16 filters (conv.hip kind 1): 5 k-steps x 64 lanes
-  const unsigned char* y2;  // [N][H][W][16] bf16, raw output of the first conv
+  const unsigned char* y2;  // [N][H][W][16] bf16, raw output of the first conv; null: never stored, formed from img (RECOMP)
+  const u32x4* wp_img;      // with y2 == null: packed FORWARD fragments of the first conv's 1 -> 16 filters (conv.hip kind 0)
   const float* scale2;      // its BatchNorm scale / shift / batch mean [16]
   const float* shift2;
   const float* mean2;
@@ -538,8 +539,14 @@ constexpr int R16_TRASH = R16_ACC + 576;
 constexpr int R16_TAB = R16_TRASH + 32;        // [4 k-groups][8] dwords: (tap, chunk) byte offsets of the five k-steps
 constexpr int B16_LDS_ROWS = R16_TAB + 128;    // 19 168
 
-template <bool SHIFTED, bool WGROWS>
+// RECOMP: y2 does not exist (Bwd16Args::y2 == null).  The pixel pass forms it from the image copies that sit in LDS for the tap
+// sums: one v_mfma_f32_16x16x16_bf16 per tile row with conv_fast.hip conv3x3_image_kernel's operands -- A = the 1 -> 16 filters
+// (row = cout r16, k-group = ky), B = (x[q], x[q + 1], x[q + 2], finite pad) of pixel column q from the copy of q's parity --
+// rounded by the same conversion: the bits that kernel would have stored, in the registers the y2 requests used to fill (D:
+// couts 4 g .. + 3 of pixel column r16).  Seven loads per tile and wave fewer, seven small MFMAs more; whole tiles only.
+template <bool SHIFTED, bool WGROWS, bool RECOMP = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHIFTED)))) void conv16_bwd_rows_kernel(Bwd16Args a) {
+  static_assert(!(RECOMP && SHIFTED), "y2 from the image: whole 14 x 14 tiles");
   constexpr int NW = 2;
   constexpr int TH = B16_TH, TW = B16_TW, HW_ = B16_HW, RP = R16_RP, PS = B16_PS;
   constexpr int NSTEPS = 5, NTHR = 64 * NW, ITER = 512 / NTHR, RPI = NTHR / 32;
@@ -611,8 +618,20 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
 
   float imgv[256 / NTHR];
   u32x4 v[ITER];
-  uint2 ypre[MW];
+  uint2 ypre[RECOMP ? 1 : MW];
   constexpr int PPT = 256 / NTHR;
+  // RECOMP: the filter fragment is requested first of all (unconditional loads, k-group 3 -- all padding -- selects zero below)
+  // and is waited for BEFORE the tile loop, where nothing younger has to arrive with it (see the traps in the file's header)
+  short wraw[3] = {0, 0, 0};
+  if (RECOMP) {
+    const int gq = min((t0 & 63) >> 4, 2);
+    const bf16_t* wq = (const bf16_t*)a.wp_img;
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int tap = 3 * gq + kx;  // packed index of (cout, ci = 0, tap): step tap >> 1, k-group 2 (tap & 1), element 0
+      wraw[kx] = (short)wq[(size_t)(((tap >> 1) * 64) + (2 * (tap & 1)) * 16 + (t0 & 15)) * 8];
+    }
+  }
   // Every global request is a buffer load: a scalar descriptor per tensor and tile (base = the tile's first halo / tile /
   // image pixel: scalar arithmetic), ONE 32-bit lane offset per request kind and a scalar row offset per request -- as
   // global loads with 64-bit lane addresses each request cost two address registers and their additions
@@ -668,7 +687,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
   if (n_first < a.N) {
     issue_img(n_first);
     issue_halo(n_first);
-    issue_y2(n_first);
+    if (!RECOMP) issue_y2(n_first);
+  }
+  uint2 wfp = {0u, 0u};  // the A fragment (s16x4) as two registers
+  if (RECOMP) {
+    const bool real = ((t0 & 63) >> 4) < 3;
+    wfp.x = real ? ((uint32_t)(unsigned short)wraw[0] | ((uint32_t)(unsigned short)wraw[1] << 16)) : 0u;
+    wfp.y = real ? (uint32_t)(unsigned short)wraw[2] : 0u;
+    asm volatile("" : "+v"(wfp.x), "+v"(wfp.y));  // (arrived and formed here, not inside the loop)
   }
   __syncthreads();  // the k-step table is read before the first staging barrier
   uint2 dzp[MW];
@@ -802,6 +828,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
     // conflicts, a third of the kernel's LDS cycles by SQ_LDS_BANK_CONFLICT)
     f32x4 ssum = {0.f, 0.f, 0.f, 0.f}, ssq = {0.f, 0.f, 0.f, 0.f};
     const unsigned xaddr = (unsigned)(R16_XT + wave * B16_XT_ROW + r16 * PS + (((g + (r16 >> 2)) & 3) << 3));
+    // RECOMP: pixel column pc (the two unused columns take 13's, as their y2 request did) of image copy pc & 1, halo row
+    // tile row + ky: (x[pc], x[pc + 1]) and (x[pc + 2], x[pc + 3]) are two aligned dwords (copy 1's column 15 is the zero pad)
+    const int pc = min(r16, TW - 1);
+    const unsigned yaddr = (unsigned)(R16_IM + (pc & 1) * 512 + ((g < 3 ? g : 0) + wave) * 32 + (pc & ~1) * 2);
     {
       const unsigned lb = (unsigned)(R16_DY + (wave * RP + r16) * PS);
       const unsigned offs[NSTEPS] = {tabA[0] + lb, tabA[1] + lb, tabA[2] + lb, tabA[3] + lb, tabB + lb};
@@ -814,8 +844,19 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
           acc = mfma_chunk<bf16_t>(wall[s], xf, acc);
         }
         const bool keep_y = !shifted || wave + NW * j >= oy;  // (wave-uniform; shifted tiles only)
-        const float yv[4] = {__uint_as_float(ypre[j].x << 16), __uint_as_float(ypre[j].x & 0xffff0000u),
-                             __uint_as_float(ypre[j].y << 16), __uint_as_float(ypre[j].y & 0xffff0000u)};
+        uint2 yr;
+        if (RECOMP) {
+          const uint2 xv = {*(const uint32_t*)(lds + yaddr + j * (NW * 32)), *(const uint32_t*)(lds + yaddr + j * (NW * 32) + 4)};
+          const f32x4 y = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, wfp), __builtin_bit_cast(s16x4, xv),
+                                                                    (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+          const f32x2 ylo = {y[0], y[1]}, yhi = {y[2], y[3]};
+          yr.x = __builtin_bit_cast(uint32_t, __builtin_convertvector(ylo, bf16x2v));
+          yr.y = __builtin_bit_cast(uint32_t, __builtin_convertvector(yhi, bf16x2v));
+        } else {
+          yr = ypre[j];
+        }
+        const float yv[4] = {__uint_as_float(yr.x << 16), __uint_as_float(yr.x & 0xffff0000u),
+                             __uint_as_float(yr.y << 16), __uint_as_float(yr.y & 0xffff0000u)};
         const f32x2 glo = {acc[0], acc[1]}, ghi = {acc[2], acc[3]};
         const uint32_t g0 = __builtin_bit_cast(uint32_t, __builtin_convertvector(glo, bf16x2v));
         const uint32_t g1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(ghi, bf16x2v));
@@ -863,7 +904,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
     }
     if (!(it + 1 < a.ipw && n + 1 < a.N)) break;
     issue_halo(n + 1);
-    issue_y2(n + 1);
+    if (!RECOMP) issue_y2(n + 1);
     issue_img(n + 1);
     second_half(n);
   }
@@ -943,16 +984,26 @@ extern "C" int spcl_conv16_bwd_fused_splits(int N, int H, int W) {
   return cdiv(H, B16_TH) * cdiv(W, B16_TW) * cdiv(N, ipw);
 }
 
-extern "C" int spcl_conv16_bwd_fused(const void* dy, int dtype, int N, int H, int W, const void* w_packed_dgrad,
-                                     const void* y2, const float* scale2, const float* shift2, const float* mean2,
-                                     const float* image, float* rows11, float* partial, float* dw_oihw, int Cin, int Cout,
-                                     float* wg_rows, const float* acorr, int nacorr, float* acorr16, void* stream) {
-  SPCL_CHECK_ARG(dy && w_packed_dgrad && y2 && scale2 && shift2 && mean2 && image && partial && dw_oihw,
+// y2 == null: the first conv's output was never stored (spcl_conv16_bwd_fused_image): w_packed_image, whole tiles of any size
+static int conv16_bwd_fused_impl(const void* dy, int dtype, int N, int H, int W, const void* w_packed_dgrad,
+                                 const void* y2, const void* w_packed_image, const float* scale2, const float* shift2,
+                                 const float* mean2, const float* image, float* rows11, float* partial, float* dw_oihw,
+                                 int Cin, int Cout, float* wg_rows, const float* acorr, int nacorr, float* acorr16,
+                                 void* stream) {
+  SPCL_CHECK_ARG(dy && w_packed_dgrad && (y2 || w_packed_image) && scale2 && shift2 && mean2 && image && partial && dw_oihw,
                  "conv16_bwd_fused: null pointer");
   SPCL_CHECK_ARG((rows11 != nullptr) != (wg_rows != nullptr), "conv16_bwd_fused: exactly one of rows11 / wg_rows");
   SPCL_CHECK_ARG(wg_rows == nullptr || (acorr && acorr16 && nacorr > 0), "conv16_bwd_fused: wg_rows comes with the autocorrelation rows");
   SPCL_CHECK_ARG(Cin > 0 && Cin <= 16 && Cout > 0 && Cout <= 16, "conv16_bwd_fused: channel counts");
-  if (!spcl_conv16_bwd_fused_supported(dtype, N, H, W, 16, 16)) {
+  if (y2 == nullptr) {
+    if (!spcl_block1_kernels_take(dtype, N, H, W, 1, 16)) {
+      set_error("conv16_bwd_fused_image: unsupported configuration (bf16, 16 -> 16 channels, H and W multiples of 14)");
+      return SPCL_EUNSUPPORTED;
+    }
+  } else if (!spcl_conv16_bwd_fused_supported(dtype, N, H, W, 16, 16) &&
+             !spcl_block1_kernels_take(dtype, N, H, W, 1, 16)) {
+    // (_supported says where the library's own dispatch runs the kernel; the call also takes the smaller whole-tile sizes:
+    // spcl_block1_kernels_take is the query for that)
     set_error("conv16_bwd_fused: unsupported configuration (bf16, 16 -> 16 channels, 14 x 14 tiles)");
     return SPCL_EUNSUPPORTED;
   }
@@ -960,6 +1011,7 @@ extern "C" int spcl_conv16_bwd_fused(const void* dy, int dtype, int N, int H, in
   spcl_wgrad_tail* tail = take_tail_capture();
   Bwd16Args a;
   a.dy = (const unsigned char*)dy; a.wp = (const u32x4*)w_packed_dgrad; a.y2 = (const unsigned char*)y2;
+  a.wp_img = (const u32x4*)w_packed_image;
   a.scale2 = scale2; a.shift2 = shift2; a.mean2 = mean2; a.img = image; a.rows11 = rows11; a.partial = partial;
   a.wg_rows = wg_rows; a.acorr_in = acorr; a.nacorr = nacorr; a.acorr_out = acorr16;
   a.N = N; a.H = H; a.W = W; a.tilesX = cdiv(W, B16_TW); a.tilesY = cdiv(H, B16_TH);
@@ -970,7 +1022,7 @@ extern "C" int spcl_conv16_bwd_fused(const void* dy, int dtype, int N, int H, in
   const int nz = cdiv(N, a.ipw), nsplit = a.tilesX * a.tilesY * nz;
   a.nwg = nsplit;
   const double px = (double)N * H * W;
-  prof_cost(px * 32.0 * 2.0 + px * 4.0 + (double)nsplit * 9 * 256 * 4.0, 2.0 * px * 9.0 * 256 * 2.0 + 2.0 * px * 9.0 * 16);
+  prof_cost(px * 32.0 * (y2 != nullptr ? 2.0 : 1.0) + px * 4.0 + (double)nsplit * 9 * 256 * 4.0, 2.0 * px * 9.0 * 256 * 2.0 + 2.0 * px * 9.0 * 16);
   a.stamps = nullptr;
   const bool want_stamps = SPCL_CONV16_STAMPS_BUILD && lab_flag("SPCL_CONV16_STAMPS");  // debug only (synchronises)
   const size_t nwg = (size_t)nsplit;
@@ -989,7 +1041,10 @@ extern "C" int spcl_conv16_bwd_fused(const void* dy, int dtype, int N, int H, in
     else if (wgr) B16_LAUNCH(true, NW_, true);              \
     else B16_LAUNCH(true, NW_, false);                      \
   }
-  if (nw == 2 && conv16_bwd_rowmap()) {
+  if (y2 == nullptr) {  // (spcl_conv16_bwd_fused_image_supported: the row-mapped kernel on whole tiles)
+    if (wgr) SPCL_LAUNCH((conv16_bwd_rows_kernel<false, true, true>), grid, dim3(128), B16_LDS_ROWS, st, a);
+    else SPCL_LAUNCH((conv16_bwd_rows_kernel<false, false, true>), grid, dim3(128), B16_LDS_ROWS, st, a);
+  } else if (nw == 2 && conv16_bwd_rowmap()) {
 #define B16_ROWS(SH_, WG_) SPCL_LAUNCH((conv16_bwd_rows_kernel<SH_, WG_>), grid, dim3(128), B16_LDS_ROWS, st, a)
     if (even && wgr) B16_ROWS(false, true);
     else if (even) B16_ROWS(false, false);
@@ -998,7 +1053,7 @@ extern "C" int spcl_conv16_bwd_fused(const void* dy, int dtype, int N, int H, in
 #undef B16_ROWS
   }
 #if SPCL_LAB  // (the linear-m-tile kernel lost its A/B in round 4: instantiated in lab builds only -- SPCL_CONV16_ROWMAP=0 / _NW)
-  else {
+  else if (y2 != nullptr) {
     B16_CASE(1) B16_CASE(2) B16_CASE(4)
   }
 #endif
@@ -1025,4 +1080,33 @@ extern "C" int spcl_conv16_bwd_fused(const void* dy, int dtype, int N, int H, in
   }
   SPCL_LAUNCH_CHECK("conv16_bwd_fused");
   return SPCL_OK;
+}
+
+extern "C" int spcl_conv16_bwd_fused(const void* dy, int dtype, int N, int H, int W, const void* w_packed_dgrad,
+                                     const void* y2, const float* scale2, const float* shift2, const float* mean2,
+                                     const float* image, float* rows11, float* partial, float* dw_oihw, int Cin, int Cout,
+                                     float* wg_rows, const float* acorr, int nacorr, float* acorr16, void* stream) {
+  SPCL_CHECK_ARG(y2 != nullptr, "conv16_bwd_fused: null pointer");
+  return conv16_bwd_fused_impl(dy, dtype, N, H, W, w_packed_dgrad, y2, nullptr, scale2, shift2, mean2, image, rows11, partial,
+                               dw_oihw, Cin, Cout, wg_rows, acorr, nacorr, acorr16, stream);
+}
+
+// spcl_conv16_bwd_fused for a first conv whose raw output y2 was never stored (unet.py:123 -> :75: the 103 MB tensor between
+// the image block's two convolutions at 64 x 224^2): the kernel forms it from `image` and that conv's packed forward weights,
+// bit for bit what spcl_conv3x3_forward_image_acorr would have stored.  The kernel takes whole 14 x 14 tiles of any image size;
+// spcl_block1_recompute_supported (conv.hip) says where the block's three launches are offered together.
+extern "C" int spcl_conv16_bwd_fused_image_supported(int dtype, int N, int H, int W, int CinK, int CoutS) {
+  return (dtype == SPCL_BF16 && CinK == 16 && CoutS == 16 && N > 0 && H >= B16_TH && W >= B16_TW && H % B16_TH == 0 &&
+          W % B16_TW == 0 && conv16_bwd_nw() == 2 && conv16_bwd_rowmap() && (double)H * W * 32.0 < 2147483648.0)
+             ? 1 : 0;
+}
+
+extern "C" int spcl_conv16_bwd_fused_image(const void* dy, int dtype, int N, int H, int W, const void* w_packed_dgrad,
+                                           const void* w_packed_image, const float* scale2, const float* shift2,
+                                           const float* mean2, const float* image, float* rows11, float* partial,
+                                           float* dw_oihw, int Cin, int Cout, float* wg_rows, const float* acorr, int nacorr,
+                                           float* acorr16, void* stream) {
+  SPCL_CHECK_ARG(w_packed_image != nullptr, "conv16_bwd_fused_image: null pointer");
+  return conv16_bwd_fused_impl(dy, dtype, N, H, W, w_packed_dgrad, nullptr, w_packed_image, scale2, shift2, mean2, image, rows11,
+                               partial, dw_oihw, Cin, Cout, wg_rows, acorr, nacorr, acorr16, stream);
 }

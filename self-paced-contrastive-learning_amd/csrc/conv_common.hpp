@@ -63,6 +63,12 @@ struct ConvArgs {
   // tile ([N * tiles][64]: 45 + 9 sums over the tile's pixels, the layout of image_autocorr_kernel's band rows) -- fast
   // path only, image sizes that are multiples of the 14 x 14 tile
   float* acorr_rows = nullptr;
+  // ... with y == nullptr: that launch leaves the statistics and autocorrelation rows only; its output is formed again per
+  // tile by the one consumer that carries img1 / wp1 -- in_mode 1 on the 16 -> 16 layer behind it (x unused: the raw input
+  // is conv(img1, wp1), one-channel f32 image [N][H][W] and the image convolution's packed forward weights) -- and by
+  // conv16_bwd.hip (fast path only, whole 14 x 14 tiles)
+  const float* img1 = nullptr;
+  const void* wp1 = nullptr;
   // BatchNorm sums through fixed-point accumulator blocks (bn_acc.hpp; fast path only -- a launch that carries one of these
   // and finds no specialised kernel FAILS, it never falls back to a kernel that would ignore them):
   long long* stats_acc = nullptr;        // the output's statistics are added here instead of written as per-tile `stats` rows

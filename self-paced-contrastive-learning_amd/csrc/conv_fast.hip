@@ -28,6 +28,7 @@ struct FastArgs {
   const float* in_shift;
   int N, H, W, CinK, CoutS, tilesX, tilesY, gy;
   unsigned long long* stamps;  // debug (SPCL_FAST_STAMPS=1): s_memtime ticks of wave 0 per phase, else null
+  int ipw;        // conv3x3_image_kernel<.., STORE = false>: images a workgroup walks at its tile position
   int lds_flip;   // bytes between the two halo images of the cross-slab pipeline (0: one image)
   int xcd_remap;  // 1: tiles of an image are dealt to the XCDs in contiguous row-major blocks (see the kernel)
   // MODE 2 (dgrad whose output g is the gradient of relu(bn(y2))): per-tile partial sums of that BatchNorm's backward
@@ -42,6 +43,10 @@ struct FastArgs {
   // sum_p dz[p][co] img[p + tap], the data-dependent part of that layer's weight gradient (dy = scale dz + A y + B: the
   // A and B terms need no pass over the activations, bn.hip image3)
   const float* img2;
+  // MODE 8 (= MODE 1 for the layer behind a one-channel f32 image whose convolution output is never stored): the input
+  // y1a = conv(img1, wp1) is formed per tile from the 18 x 18 image halo, as conv3x3_image_kernel forms it (x unused)
+  const float* img1;
+  const u32x4* wp1;  // packed forward weights of that image convolution (kind 0, CinK = 16)
   float* acorr_rows;  // conv3x3_image_kernel<.., ACORR = true>: [tile][64] autocorrelation partial rows of the image (ConvArgs::acorr_rows)
   // BatchNorm sums as fixed-point accumulator blocks (bn_acc.hpp) instead of per-tile rows + a reduction launch:
   long long* stats_acc;  // non-null: the output's sum x, sum x^2 are ADDED here (`stats` is then ignored)
@@ -110,7 +115,7 @@ constexpr int fast_wpe(int KC, int TH, int NW, int NT, int MODE = 0) {
   int w = (wgs * NW + 3) / 4;
   w = w > 4 ? 4 : (w < 1 ? 1 : w);
   const int acc = (SPCL_FAST_ROWMAP ? TH : (TH * 14 + 15) / 16) * NT * 4;  // accumulator registers of a wave
-  if (KC == 16 && MODE >= 2 && SPCL_FAST_YPRE_MINKC <= 16 && w > 3 && acc <= 80) return 3;  // room for the y2 requests
+  if (KC == 16 && MODE >= 2 && MODE <= 4 && SPCL_FAST_YPRE_MINKC <= 16 && w > 3 && acc <= 80) return 3;  // room for the y2 requests
   if (acc > 80 && w > 2) return 2;               // 13 m-tiles x 2 n-tiles: give the allocator 256 registers
   // 9-step ring of one n-tile: 36 registers.  Four-wave workgroups (every 64 -> 64 layer): three waves per SIMD = three
   // workgroups per CU since the row order freed the m-tile bases (168 registers, one harmless address spill)
@@ -190,7 +195,13 @@ conv3x3_fast_kernel(FastArgs a) {
   // prologue from a fixed-point accumulator block (bn_acc.hpp), the block's eight replicas of a channel split over 4 / 2 / 1
   // threads (= workgroup threads / input channels).  Instantiations of their own: the prologue's registers (2 / 4 / 8 replicas
   // x 32 bytes in flight per thread) are allocated for the form present, and must not weigh on the block 1 / 2 kernels at all
-  constexpr bool M1 = MODE == 1 || MODE >= 5;
+  constexpr bool M1 = MODE == 1 || (MODE >= 5 && MODE <= 7);
+  // MODE 8 = MODE 1 whose input tensor does not exist: the raw output y1a of the one-channel image convolution in front (unet.py:123)
+  // is formed HERE, on the 16 x 16 halo, from the 18 x 18 f32 image halo -- one v_mfma_f32_16x16x16_bf16 per halo row with the
+  // operands conv3x3_image_kernel (below) builds, rounded to bf16 by the same conversion: the bits that kernel would have stored.
+  // Then scale / shift + ReLU as MODE 1 applies them to a loaded value, zero at halo pixels outside the image.
+  constexpr bool M8 = MODE == 8;
+  static_assert(!M8 || (KC == 16 && TH == 14 && NT == 1 && NW == 1), "MODE 8: the 16 -> 16 layer on 14 x 14 tiles, one wave");
   constexpr int ACC_TPC = MODE == 5 ? 4 : (MODE == 6 ? 2 : 1);
   // MODE 4: the lane's four pixels of the 16 x 16 image halo (row lane / 4, columns 4 (lane % 4) ..), zero outside the
   // image; parked in registers across the k-loop, written to LDS when the activation halo is no longer needed
@@ -263,6 +274,12 @@ conv3x3_fast_kernel(FastArgs a) {
   const size_t wstep = (size_t)ntn * 1024;                  // bytes per k-step
   u32x4 v[ITER];
   float ssc[8], ssh[8];
+  // (MODE 8: the image halo's registers, the image convolution's A fragment, scale / shift of the lane's four channels)
+  constexpr int IW8 = 18;
+  float imv8[M8 ? 6 : 1];
+  s16x4 wfrag8 = {0, 0, 0, 0};
+  f32x4 sc8 = {0.f, 0.f, 0.f, 0.f}, sh8 = {0.f, 0.f, 0.f, 0.f};
+  const int ir8 = lane / IW8, ic8 = lane - ir8 * IW8;
   constexpr bool STREAM_W = PRELOAD_SLAB && KC == 64;  // (the only shape with more than one slab)
   constexpr int WR = STREAM_W ? (NT == 1 ? SPCL_FAST_WR_NT1 : 9) : (PRELOAD_SLAB ? NSTEPS : 1);
   u32x4 wsl[WR][NT];
@@ -271,7 +288,7 @@ conv3x3_fast_kernel(FastArgs a) {
   // derives scale / shift and parks them in LDS behind the halo image(s); every thread then takes its chunk's eight from there
   // (slab 0: after the barrier below; later slabs: plain LDS reads).  The first workgroup of the launch also writes mean /
   // invstd / scale / shift and the running statistics (what the finalize launch used to leave for backward / eval).
-  constexpr bool acc_in = MODE >= 5;
+  constexpr bool acc_in = MODE >= 5 && MODE <= 7;
   float* const coef_l = (float*)(lds + fast_lds_bytes(KC, TH) * (a.lds_flip != 0 ? 2 : 1));  // [2][CinK]
   auto load_coef_lds = [&](int slab) {
     const int cc = two_chunks ? ch1 : ch;
@@ -348,7 +365,66 @@ conv3x3_fast_kernel(FastArgs a) {
         if (in_range) *(u32x4*)(lpw + (dky * RP + dkx) * PS) = tv;
       }
     };
-    if (M1 && !interior) stage(std::false_type{});
+    if constexpr (M8) {
+      // the image halo as bf16 pairs (x[q], x[q + 1]) per pixel q: a lane's B fragment (x[q] .. x[q + 3]: three taps and a
+      // finite pad against a zero weight) is pairs q and q + 2.  Written as halves: a lane puts its pixel into the lower half of
+      // its own pair and into the upper half of its left-hand neighbour's, column 17 also a zero into its own upper half -- every
+      // store of the wave has an address of its own (no cross-lane move, and no order among the stores to rely on); read as dwords
+      // behind the barrier
+      typedef uint32_t __attribute__((may_alias)) pair_t;
+      typedef unsigned short __attribute__((may_alias)) half_t;
+      const pair_t* const pairs = (const pair_t*)lds;  // [18][18], in the halo image's place: its pixels wait in registers
+      half_t* const halves = (half_t*)lds;
+      unsigned short pb8[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        const f32x2 pv = {imv8[k], 0.f};
+        pb8[k] = (unsigned short)__builtin_bit_cast(uint32_t, __builtin_convertvector(pv, bf16x2v));
+      }
+      if (lane < 3 * IW8) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) halves[2 * ((ir8 + 3 * k) * IW8 + ic8)] = pb8[k];
+        if (ic8 > 0) {
+#pragma unroll
+          for (int k = 0; k < 6; ++k) halves[2 * ((ir8 + 3 * k) * IW8 + ic8) - 1] = pb8[k];
+        }
+        if (ic8 == IW8 - 1) {
+#pragma unroll
+          for (int k = 0; k < 6; ++k) halves[2 * ((ir8 + 3 * k) * IW8 + ic8) + 1] = 0;
+        }
+      }
+      __syncthreads();  // (one wave: an ordering point for the dword reads below)
+      const int gx = x0 - 1 + r16;
+      const bool colin = gx >= 0 && gx < a.W;
+      const int gg = g < 3 ? g : 0;  // k-group 3 is all padding (zero weights): read something valid
+      uint2 hv[HW_];
+#pragma unroll
+      for (int hy = 0; hy < TH + 2; ++hy) {
+        const pair_t* src = pairs + (hy + gg) * IW8 + r16;
+        const uint2 xv = {src[0], src[2]};
+        const f32x4 y = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(wfrag8, __builtin_bit_cast(s16x4, xv),
+                                                                  (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        // lane: couts 4 g .. + 3 of halo pixel (hy, r16), rounded as the image kernel stores them
+        const f32x2 ylo = {y[0], y[1]}, yhi = {y[2], y[3]};
+        const uint32_t p0 = __builtin_bit_cast(uint32_t, __builtin_convertvector(ylo, bf16x2v));
+        const uint32_t p1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(yhi, bf16x2v));
+        const u32x4 raw = {p0, p1, 0u, 0u};
+        const float s4[8] = {sc8[0], sc8[1], sc8[2], sc8[3], 0.f, 0.f, 0.f, 0.f};
+        const float b4[8] = {sh8[0], sh8[1], sh8[2], sh8[3], 0.f, 0.f, 0.f, 0.f};
+        const u32x4 tv = bnrelu_regs<bf16_t>(raw, s4, b4);  // (MODE 1's arithmetic; the upper half folds away)
+        hv[hy] = (uint2){tv[0], tv[1]};
+      }
+      if (!interior) {  // zero padding applies to the ACTIVATION: 0 at a halo pixel outside the image, not relu(shift)
+#pragma unroll
+        for (int hy = 0; hy < TH + 2; ++hy) {
+          const int gy = y0 - 1 + hy;
+          if (!(colin && gy >= 0 && gy < a.H)) hv[hy] = (uint2){0u, 0u};
+        }
+      }
+      __syncthreads();  // every pair has been read: the halo image takes their place
+#pragma unroll
+      for (int hy = 0; hy < TH + 2; ++hy) *(uint2*)(lds + (hy * RP + r16) * PS + g * 8) = hv[hy];
+    } else if (M1 && !interior) stage(std::false_type{});
     else stage(std::true_type{});
     if (refill) issue_halo(slab + 1);
     if (stamp && slab == 0) t_store = __builtin_amdgcn_s_memtime();
@@ -433,7 +509,33 @@ conv3x3_fast_kernel(FastArgs a) {
     accp.load(a.in_bn.acc, a.CinK, acc_c, acc_has ? ACC_RPT * acc_part : 0);
     accprm.load(a.in_bn, acc_c);
   }
-  issue_halo(0, true);
+  // MODE 8: the image halo (origin (y0 - 2, x0 - 2)): lane -> column lane % 18 of the rows lane / 18 + 3 k, lanes 0 .. 53; one
+  // clamped load per pixel, zero outside the image
+  if constexpr (M8) {
+    const float* im = a.img1 + (size_t)n * a.H * a.W;
+    const int gx = x0 - 2 + ic8;
+    const bool colok = gx >= 0 && gx < a.W;
+    const int gxc = gx < 0 ? 0 : (gx >= a.W ? a.W - 1 : gx);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const int gy = y0 - 2 + ir8 + 3 * k;
+      const int gyc = gy < 0 ? 0 : (gy >= a.H ? a.H - 1 : gy);
+      const float raw = im[(size_t)gyc * a.W + gxc];
+      imv8[k] = (colok && gy >= 0 && gy < a.H) ? raw : 0.f;
+    }
+    if (g < 3) {  // the A fragment of conv3x3_image_kernel: row = cout r16, k-group g = ky: W[cout][0][ky][0 .. 2], 0
+      const bf16_t* wq = (const bf16_t*)a.wp1;
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int tap = 3 * g + kx;
+        wfrag8[kx] = (short)wq[(size_t)(((tap >> 1) * 64) + (2 * (tap & 1)) * 16 + r16) * 8];
+      }
+    }
+    sc8 = *(const f32x4*)(a.in_scale + 4 * g);
+    sh8 = *(const f32x4*)(a.in_shift + 4 * g);
+  } else {
+    issue_halo(0, true);
+  }
   if (PRELOAD_SLAB) {
 #pragma unroll
     for (int s = 0; s < WR; ++s)
@@ -816,7 +918,9 @@ conv3x3_fast_kernel(FastArgs a) {
 // of 16 columns, the last two masked), A = B = the patch matrix (one ds_read2_b32 pair per operand), a second accumulator
 // against a ones operand for the image sums: 14 MFMAs and ~60 instructions per tile instead of a 13 MB pass of its own
 // (image_autocorr_body in the weight-pack launch: ~15 us of the step's first launch).  EVEN sizes only.
-template <int TH, bool EVEN, bool ACORR = false>
+// STORE = false: everything but the output stream -- the statistics rows (from the f32 accumulators, in the same order) and the
+// autocorrelation rows, bit for bit; y is formed again where it is needed (conv3x3_fast_kernel MODE 8, conv16_bwd.hip)
+template <int TH, bool EVEN, bool ACORR = false, bool STORE = true>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void conv3x3_image_kernel(FastArgs a) {
   constexpr int TW = 14, HW_ = 16, LW = HW_ + 2;  // LDS row: 16 halo pixels + 2 so that pair q+2 of the last tap exists
   constexpr bool RM = SPCL_FAST_ROWMAP != 0;  // m-tile i = tile row i, pixel column r16 (see conv3x3_fast_kernel)
@@ -824,7 +928,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void co
   __shared__ uint32_t pairs[(TH + 2) * LW];
   const int lane = threadIdx.x, r16 = lane & 15, g = lane >> 4;
   int tx = blockIdx.x, ty = blockIdx.y;
-  const int n = blockIdx.z;
+  // STORE = false: a workgroup walks a.ipw images at its tile position, the next image's halo requested while this one is worked
+  // on.  One 64-thread workgroup per tile is 16 384 short load -> LDS -> MFMA -> store chains at 64 x 224^2 with nothing to overlap
+  // them and their start-up (measured without the stores: 17.5 us where the storing kernel took 22.4; as ~4 096 workgroups of four
+  // images: 15.2 against 22.1).  Same tiles, same arithmetic per tile: the rows keep their bits.
+  const int n_first = STORE ? (int)blockIdx.z : (int)blockIdx.z * a.ipw;
+  const int n_end = STORE ? n_first + 1 : min(n_first + a.ipw, a.N);
   {  // (an XCD's workgroups take neighbouring tiles: the 128-byte lines two tiles of a row share are completed in ONE L2)
     const int T = a.tilesX * a.tilesY;
     if (a.xcd_remap && (T & 7) == 0) {
@@ -836,7 +945,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void co
   }
   const int y0 = min(ty * TH, a.H - TH), x0 = min(tx * TW, a.W - TW);  // shifted last tiles, as in the kernel above
   const int oy = ty * TH - y0, ox = tx * TW - x0;
-  const int tile = (n * a.tilesY + ty) * a.tilesX + tx;
 
   // A fragment: row = cout r16, k-group g = ky: W[cout][0][ky][0..2], 0.  Packed index of (cout, ci = 0, tap):
   // chunk fc = 2 tap -> step tap >> 1, k-group 2 (tap & 1), element 0
@@ -853,140 +961,156 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void co
   // stage: lane -> halo pixels q = lane + 64 k (four halo rows of 16 per step: a lane keeps its column); pair =
   // (x[q], x[q+1]) with zero outside the image -- ONE clamped load per pixel, the right-hand neighbour comes from the next
   // lane (the second load and its bounds checks were a third of the staging's instructions; the kernel is issue-bound)
-  const float* img = (const float*)a.x + (size_t)n * a.H * a.W;
-  {
-    const int hx = r16, gx = x0 - 1 + hx;
-    const bool colok = gx >= 0 && gx < a.W;
-    const int gxc = gx < 0 ? 0 : (gx >= a.W ? a.W - 1 : gx);
+  constexpr int NK = (NHALO + 63) / 64;
+  const int gx = x0 - 1 + r16;
+  const bool colok = gx >= 0 && gx < a.W;
+  const int gxc = gx < 0 ? 0 : (gx >= a.W ? a.W - 1 : gx);
+  float raw[NK];
+  auto request = [&](const int n) {
+    const float* img = (const float*)a.x + (size_t)n * a.H * a.W;
 #pragma unroll
-    for (int k = 0; k < (NHALO + 63) / 64; ++k) {
-      const int hy = g + 4 * k;
-      const int gy = y0 - 1 + hy;
+    for (int k = 0; k < NK; ++k) {
+      const int gy = y0 - 1 + g + 4 * k;
       const int gyc = gy < 0 ? 0 : (gy >= a.H ? a.H - 1 : gy);
-      const float raw = img[(size_t)gyc * a.W + gxc];
-      const float v0 = (colok && gy >= 0 && gy < a.H) ? raw : 0.f;
-      float v1 = __shfl_down(v0, 1, 64);
-      if (hx == HW_ - 1) v1 = 0.f;
-      const f32x2 pv = {v0, v1};
-      if (NHALO % 64 == 0 || hy < TH + 2) pairs[hy * LW + hx] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pv, bf16x2v));
+      raw[k] = img[(size_t)gyc * a.W + gxc];
     }
-  }
-  if (lane < 2 * (TH + 2)) pairs[(lane >> 1) * LW + HW_ + (lane & 1)] = 0u;  // the two pad pairs of each row
-  __syncthreads();
-
-  f32x4 acc[MT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    int p = 16 * i + r16;
-    if (p >= NPIX) p = 0;
-    const int py = RM ? i : p / TW, px = RM ? r16 : p - py * TW;  // (row order: columns 14, 15 read the pad pairs; unused)
-    const int gg = g < 3 ? g : 0;  // k-group 3 is all padding (zero weights): read something valid
-    const uint32_t* src = pairs + (py + gg) * LW + px;
-    const uint32_t lo = src[0], hi = src[2];
-    const uint2 xv = {lo, hi};
-    acc[i] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(wfrag, __builtin_bit_cast(s16x4, xv),
-                                                       (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  }
-
-  constexpr int DPY = RM ? 1 : 16 / TW, DPX = RM ? 0 : 16 % TW;
-  const int rowb = a.CoutS * 2;
-  unsigned char* yb = a.y + (((size_t)n * a.H + y0) * a.W + x0) * rowb + 4 * g * 2;
-  int py = RM ? 0 : r16 / TW, px = r16 - py * TW;
-  int ob = (py * a.W + px) * rowb;
-  const int dob = (DPY * a.W + DPX) * rowb, wrapo = (a.W - TW) * rowb;
-  f32x4 ssum = {0.f, 0.f, 0.f, 0.f}, ssq = {0.f, 0.f, 0.f, 0.f};
-  const bool shifted = !EVEN && (oy | ox) != 0;
-  int pyc = py;
-  // Two m-tiles per 16-byte store: lanes g and g ^ 1 hold the two 8-byte halves of a pixel's 16-byte channel run, so one
-  // v_permlane16_swap per dword gives the even lane group both halves of its pixel in m-tile i and the odd one both halves of
-  // its pixel in m-tile i + 1 -- half the store instructions for the same bytes (the kernel is a 103 MB output stream).
-  uint2 pk[MT];
-  int obs[MT];
-  if (!RM || r16 < TW) {  // (row order: the two unused pixel columns are off for the whole epilogue)
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const bool ok = RM || (16 * i + 15 < NPIX) || (16 * i + r16 < NPIX);
-    obs[i] = ob;
+  };
+  request(n_first);
+#pragma unroll 1
+  for (int n = n_first; n < n_end; ++n) {
+    const int tile = (n * a.tilesY + ty) * a.tilesX + tx;
+    if (!STORE && n > n_first) __syncthreads();  // (one wave: the previous image's reads of `pairs` come first)
     {
-      const f32x2 lo = {acc[i][0], acc[i][1]}, hi = {acc[i][2], acc[i][3]};
-      pk[i].x = __builtin_bit_cast(uint32_t, __builtin_convertvector(lo, bf16x2v));
-      pk[i].y = __builtin_bit_cast(uint32_t, __builtin_convertvector(hi, bf16x2v));
-    }
-    if (ok) {
-      if (EVEN) {
-        ssum += acc[i];
-        ssq += acc[i] * acc[i];
-      } else {
-        const float keep = (!shifted || (pyc >= oy && px >= ox)) ? 1.f : 0.f;
-        const f32x4 av = acc[i] * keep;
-        ssum += av;
-        ssq += av * acc[i];
+      const int hx = r16;
+#pragma unroll
+      for (int k = 0; k < NK; ++k) {
+        const int hy = g + 4 * k;
+        const int gy = y0 - 1 + hy;
+        const float v0 = (colok && gy >= 0 && gy < a.H) ? raw[k] : 0.f;
+        float v1 = __shfl_down(v0, 1, 64);
+        if (hx == HW_ - 1) v1 = 0.f;
+        const f32x2 pv = {v0, v1};
+        if (NHALO % 64 == 0 || hy < TH + 2) pairs[hy * LW + hx] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pv, bf16x2v));
       }
     }
-    px += DPX;
-    pyc += DPY;
-    ob += dob;
-    if (!RM && px >= TW) {
-      px -= TW;
-      pyc += 1;
-      ob += wrapo;
+    if (!STORE && n + 1 < n_end) request(n + 1);
+    if (lane < 2 * (TH + 2)) pairs[(lane >> 1) * LW + HW_ + (lane & 1)] = 0u;  // the two pad pairs of each row
+    __syncthreads();
+
+    f32x4 acc[MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      int p = 16 * i + r16;
+      if (p >= NPIX) p = 0;
+      const int py = RM ? i : p / TW, px = RM ? r16 : p - py * TW;  // (row order: columns 14, 15 read the pad pairs; unused)
+      const int gg = g < 3 ? g : 0;  // k-group 3 is all padding (zero weights): read something valid
+      const uint32_t* src = pairs + (py + gg) * LW + px;
+      const uint32_t lo = src[0], hi = src[2];
+      const uint2 xv = {lo, hi};
+      acc[i] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(wfrag, __builtin_bit_cast(s16x4, xv),
+                                                         (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
     }
-  }
-  constexpr int NPAIR = SPCL_FAST_WIDE_STORES ? (RM ? MT / 2 : (NPIX / 16) / 2) : 0;  // pairs of COMPLETE m-tiles
+
+    constexpr int DPY = RM ? 1 : 16 / TW, DPX = RM ? 0 : 16 % TW;
+    const int rowb = a.CoutS * 2;
+    unsigned char* yb = a.y + (((size_t)n * a.H + y0) * a.W + x0) * rowb + 4 * g * 2;
+    int py = RM ? 0 : r16 / TW, px = r16 - py * TW;
+    int ob = (py * a.W + px) * rowb;
+    const int dob = (DPY * a.W + DPX) * rowb, wrapo = (a.W - TW) * rowb;
+    f32x4 ssum = {0.f, 0.f, 0.f, 0.f}, ssq = {0.f, 0.f, 0.f, 0.f};
+    const bool shifted = !EVEN && (oy | ox) != 0;
+    int pyc = py;
+    // Two m-tiles per 16-byte store: lanes g and g ^ 1 hold the two 8-byte halves of a pixel's 16-byte channel run, so one
+    // v_permlane16_swap per dword gives the even lane group both halves of its pixel in m-tile i and the odd one both halves of
+    // its pixel in m-tile i + 1 -- half the store instructions for the same bytes (the kernel is a 103 MB output stream).
+    uint2 pk[MT];
+    int obs[MT];
+    if (!RM || r16 < TW) {  // (row order: the two unused pixel columns are off for the whole epilogue)
 #pragma unroll
-  for (int p = 0; p < NPAIR; ++p) {
-    const int i = 2 * p;
-    const auto rx = __builtin_amdgcn_permlane16_swap(pk[i].x, pk[i + 1].x, false, false);
-    const auto ry = __builtin_amdgcn_permlane16_swap(pk[i].y, pk[i + 1].y, false, false);
-    const u32x4 v = {rx[0], ry[0], rx[1], ry[1]};
-    *(u32x4*)(yb + ((g & 1) ? obs[i + 1] - 8 : obs[i])) = v;
-  }
+    for (int i = 0; i < MT; ++i) {
+      const bool ok = RM || (16 * i + 15 < NPIX) || (16 * i + r16 < NPIX);
+      if (STORE) {
+        obs[i] = ob;
+        const f32x2 lo = {acc[i][0], acc[i][1]}, hi = {acc[i][2], acc[i][3]};
+        pk[i].x = __builtin_bit_cast(uint32_t, __builtin_convertvector(lo, bf16x2v));
+        pk[i].y = __builtin_bit_cast(uint32_t, __builtin_convertvector(hi, bf16x2v));
+      }
+      if (ok) {
+        if (EVEN) {
+          ssum += acc[i];
+          ssq += acc[i] * acc[i];
+        } else {
+          const float keep = (!shifted || (pyc >= oy && px >= ox)) ? 1.f : 0.f;
+          const f32x4 av = acc[i] * keep;
+          ssum += av;
+          ssq += av * acc[i];
+        }
+      }
+      px += DPX;
+      pyc += DPY;
+      ob += dob;
+      if (!RM && px >= TW) {
+        px -= TW;
+        pyc += 1;
+        ob += wrapo;
+      }
+    }
+    constexpr int NPAIR = !STORE ? 0 : (SPCL_FAST_WIDE_STORES ? (RM ? MT / 2 : (NPIX / 16) / 2) : 0);  // pairs of COMPLETE m-tiles
 #pragma unroll
-  for (int i = 2 * NPAIR; i < MT; ++i) {
-    const bool ok = RM || (16 * i + 15 < NPIX) || (16 * i + r16 < NPIX);
-    if (ok) *(uint2*)(yb + obs[i]) = pk[i];
-  }
-  }
-  if (a.stats != nullptr)
-    write_tile_stats(a.stats, tile, a.CoutS, 4 * g, r16, (float)((TH - oy) * (TW - ox)), ssum, ssq);
-  if (ACORR) {
-    static_assert(!ACORR || (EVEN && TH % 2 == 0), "autocorrelation rows: whole 14 x 14 tiles");
-    __shared__ float dsum[2][16][16];
-    const int tap = r16 < 9 ? r16 : 0, ky = tap / 3, kx = tap - 3 * ky;
-    // lane (tap r16, k-group g): pixels 8 (g & 1) .. + 7 of tile row 2 ks + (g >> 1), shifted by the tap = halo pairs
-    // s, s + 2, s + 4, s + 6 with s = (row + ky) LW + 8 (g & 1) + kx; pixel columns 14, 15 (the last pair of the upper
-    // k-groups) are not the tile's: zero in A, so their products vanish whatever B holds
-    const uint32_t* src = pairs + ((g >> 1) + ky) * LW + 8 * (g & 1) + kx;
-    const bool upper = (g & 1) != 0;
-    const u32x4 ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
-    f32x4 D = {0.f, 0.f, 0.f, 0.f}, S = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < TH / 2; ++ks) {
-      const uint32_t* q = src + ks * 2 * LW;
-      const u32x4 fb = {q[0], q[2], q[4], q[6]};
-      u32x4 fa = fb;
-      fa[3] = upper ? 0u : fb[3];
-      D = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, fb), D, 0, 0, 0);
-      S = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, ones), S, 0, 0, 0);
+    for (int p = 0; p < NPAIR; ++p) {
+      const int i = 2 * p;
+      const auto rx = __builtin_amdgcn_permlane16_swap(pk[i].x, pk[i + 1].x, false, false);
+      const auto ry = __builtin_amdgcn_permlane16_swap(pk[i].y, pk[i + 1].y, false, false);
+      const u32x4 v = {rx[0], ry[0], rx[1], ry[1]};
+      *(u32x4*)(yb + ((g & 1) ? obs[i + 1] - 8 : obs[i])) = v;
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {  // D[row t' = 4 g + r][column t = r16]; every column of S holds the row's image sum
-      dsum[0][4 * g + r][r16] = D[r];
-      dsum[1][4 * g + r][r16] = S[r];
+    for (int i = 2 * NPAIR; i < MT; ++i) {
+      const bool ok = RM || (16 * i + 15 < NPIX) || (16 * i + r16 < NPIX);
+      if (STORE && ok) *(uint2*)(yb + obs[i]) = pk[i];
     }
-    __syncthreads();  // (one wave: an ordering point)
-    const int k = lane;
-    float v = 0.f;
-    if (k < 45) {  // upper triangle in the order of bn.hip acorr_index: row ra = number of row starts <= k
-      int ra = 0;
+    }
+    if (a.stats != nullptr)
+      write_tile_stats(a.stats, tile, a.CoutS, 4 * g, r16, (float)((TH - oy) * (TW - ox)), ssum, ssq);
+    if (ACORR) {
+      static_assert(!ACORR || (EVEN && TH % 2 == 0), "autocorrelation rows: whole 14 x 14 tiles");
+      __shared__ float dsum[2][16][16];
+      const int tap = r16 < 9 ? r16 : 0, ky = tap / 3, kx = tap - 3 * ky;
+      // lane (tap r16, k-group g): pixels 8 (g & 1) .. + 7 of tile row 2 ks + (g >> 1), shifted by the tap = halo pairs
+      // s, s + 2, s + 4, s + 6 with s = (row + ky) LW + 8 (g & 1) + kx; pixel columns 14, 15 (the last pair of the upper
+      // k-groups) are not the tile's: zero in A, so their products vanish whatever B holds
+      const uint32_t* src = pairs + ((g >> 1) + ky) * LW + 8 * (g & 1) + kx;
+      const bool upper = (g & 1) != 0;
+      const u32x4 ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
+      f32x4 D = {0.f, 0.f, 0.f, 0.f}, S = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int i = 1; i < 9; ++i) ra += k >= i * 9 - i * (i - 1) / 2 ? 1 : 0;
-      const int cb = ra + (k - (ra * 9 - ra * (ra - 1) / 2));
-      v = dsum[0][ra][cb];
-    } else if (k < 54) {
-      v = dsum[1][k - 45][0];
+      for (int ks = 0; ks < TH / 2; ++ks) {
+        const uint32_t* q = src + ks * 2 * LW;
+        const u32x4 fb = {q[0], q[2], q[4], q[6]};
+        u32x4 fa = fb;
+        fa[3] = upper ? 0u : fb[3];
+        D = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, fb), D, 0, 0, 0);
+        S = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, ones), S, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {  // D[row t' = 4 g + r][column t = r16]; every column of S holds the row's image sum
+        dsum[0][4 * g + r][r16] = D[r];
+        dsum[1][4 * g + r][r16] = S[r];
+      }
+      __syncthreads();  // (one wave: an ordering point)
+      const int k = lane;
+      float v = 0.f;
+      if (k < 45) {  // upper triangle in the order of bn.hip acorr_index: row ra = number of row starts <= k
+        int ra = 0;
+#pragma unroll
+        for (int i = 1; i < 9; ++i) ra += k >= i * 9 - i * (i - 1) / 2 ? 1 : 0;
+        const int cb = ra + (k - (ra * 9 - ra * (ra - 1) / 2));
+        v = dsum[0][ra][cb];
+      } else if (k < 54) {
+        v = dsum[1][k - 45][0];
+      }
+      a.acorr_rows[(size_t)tile * 64 + k] = v;
     }
-    a.acorr_rows[(size_t)tile * 64 + k] = v;
   }
 }
 
@@ -1013,6 +1137,9 @@ static void launch_fast(const FastArgs& a, int mode, hipStream_t st) {
   if (a.img2 != nullptr) {
     if constexpr (KC == 16 && TH == 14 && NT == 1 && NW == 1)
       SPCL_LAUNCH((conv3x3_fast_kernel<KC, TH, NT, 4, NW>), grid, block, lds, st, b);
+  } else if (mode == 8) {
+    if constexpr (KC == 16 && TH == 14 && NT == 1 && NW == 1)
+      SPCL_LAUNCH((conv3x3_fast_kernel<KC, TH, NT, 8, NW>), grid, block, lds, st, b);
   } else if (mode == 1 && a.in_bn.acc != nullptr) {
     if constexpr (KC == 64) {  // (threads per input channel; launch_conv_fast has checked that it is 4, 2 or 1)
       const int tpc = 64 * NW / a.CinK;
@@ -1055,12 +1182,20 @@ bool launch_conv_fast(const ConvArgs& c, int th, hipStream_t st, bool dry) {
     static const int env_img_remap = lab_env("SPCL_IMAGE_XCD_REMAP", 1);
     a.tilesX = cdiv(c.W, 14); a.tilesY = cdiv(c.H, 14); a.gy = 1; a.xcd_remap = env_img_remap; a.lds_flip = 0; a.stamps = nullptr;
     a.acorr_rows = c.acorr_rows;
+    a.img1 = nullptr; a.wp1 = nullptr; a.ipw = 1;
     a.stats_acc = a.rows2_acc = nullptr;
     a.in_bn = BnAccFwd{};
     if (c.stats_acc != nullptr || c.rows2_acc != nullptr || c.in_bn != nullptr) return false;  // (16 384 tiles: rows + reduction)
     if (c.acorr_rows != nullptr && !(c.H % 14 == 0 && c.W % 14 == 0)) return false;  // (whole tiles only)
+    if (c.y == nullptr && !dry && c.acorr_rows == nullptr) return false;  // (the statistics-only form exists with ACORR)
     if (!dry) {
-      if (c.acorr_rows != nullptr) SPCL_LAUNCH((conv3x3_image_kernel<14, true, true>), dim3(a.tilesX, a.tilesY, a.N), dim3(64), 0, st, a);
+      if (c.acorr_rows != nullptr && c.y == nullptr) {
+        // about 4 096 workgroups (two thirds of the 28 waves per CU the kernel's registers allow on 256 CUs), each walking ipw images
+        a.ipw = (int)(((long)a.tilesX * a.tilesY * a.N + 4095) / 4096);
+        a.ipw = a.ipw < 1 ? 1 : (a.ipw > a.N ? a.N : a.ipw);
+        SPCL_LAUNCH((conv3x3_image_kernel<14, true, true, false>), dim3(a.tilesX, a.tilesY, cdiv(a.N, a.ipw)), dim3(64), 0, st, a);
+      }
+      else if (c.acorr_rows != nullptr) SPCL_LAUNCH((conv3x3_image_kernel<14, true, true>), dim3(a.tilesX, a.tilesY, a.N), dim3(64), 0, st, a);
       else if (c.H % 14 == 0 && c.W % 14 == 0) SPCL_LAUNCH((conv3x3_image_kernel<14, true>), dim3(a.tilesX, a.tilesY, a.N), dim3(64), 0, st, a);
       else SPCL_LAUNCH((conv3x3_image_kernel<14, false>), dim3(a.tilesX, a.tilesY, a.N), dim3(64), 0, st, a);
     }
@@ -1135,6 +1270,12 @@ bool launch_conv_fast(const ConvArgs& c, int th, hipStream_t st, bool dry) {
   a.H2 = c.H2; a.W2 = c.W2;
   a.img2 = c.img2;
   a.acorr_rows = nullptr;
+  // (the input formed from the image: the 16 -> 16 layer on whole 14 x 14 tiles, coefficients from arrays, rows for statistics)
+  a.img1 = c.img1; a.wp1 = (const u32x4*)c.wp1; a.ipw = 1;
+  if (c.img1 != nullptr && !(c.in_mode == 1 && KC == 16 && th == 14 && ntn == 1 && c.x2 == nullptr && c.y_hi == nullptr &&
+                             !c.x_up2 && c.rows2 == nullptr && c.img2 == nullptr && !wants_acc && c.H % 14 == 0 && c.W % 14 == 0 &&
+                             (dry || (c.wp1 != nullptr && c.in_scale != nullptr && c.in_shift != nullptr))))
+    return false;
   // fixed-point accumulator blocks (bn_acc.hpp): plain one-tensor-output launches with few enough tiles (same-address adds
   // serialise at the memory side: ~18 ns each, tiles / 8 of them per address); the prologue form needs 4, 2 or 1 threads per
   // input channel
@@ -1163,7 +1304,7 @@ bool launch_conv_fast(const ConvArgs& c, int th, hipStream_t st, bool dry) {
   if (c.rows2 != nullptr && c.H2 > 0 && KC == 64 && nw == 1) return false;
 #define SPCL_FAST_CASE(KC_, TH_, NT_, NW_)                               \
   if (KC == KC_ && th == TH_ && NT == NT_ && nw == NW_) {                \
-    if (!dry) launch_fast<KC_, TH_, NT_, NW_>(a, c.in_mode, st);         \
+    if (!dry) launch_fast<KC_, TH_, NT_, NW_>(a, c.img1 != nullptr ? 8 : c.in_mode, st); \
     return true;                                                         \
   }
   SPCL_FAST_CASE(16, 14, 1, 1)  // Conv1.b forward / dgrad (16 -> 16 @ 224^2)

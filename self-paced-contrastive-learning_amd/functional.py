@@ -1000,11 +1000,12 @@ def _acorr_in_conv_rows(dt_code, N, H, W, cin=1, cout_s=16):
     return _n.call("spcl_conv3x3_forward_image_acorr_rows", dt_code, N, H, W, cin, cout_s)
 
 
-def _conv_image_acorr(x_store, dt_code, dtype, N, H, W, cin_s, cout_s, wp, want_stats, rows):
+def _conv_image_acorr(x_store, dt_code, dtype, N, H, W, cin_s, cout_s, wp, want_stats, rows, store=True):
     """the one-channel image convolution + the image's autocorrelation rows in ONE launch
-    (spcl_conv3x3_forward_image_acorr) -> (y, stats, acorr [rows][64])"""
+    (spcl_conv3x3_forward_image_acorr) -> (y, stats, acorr [rows][64]); ``store=False``: the statistics-only form, y is None
+    (the same rows bit for bit; the block's other launches form y again per tile: ``_BLOCK1_RECOMPUTE``)"""
     dev = x_store.device
-    y = torch.empty(N, H, W, cout_s, dtype=dtype, device=dev)
+    y = torch.empty(N, H, W, cout_s, dtype=dtype, device=dev) if store else None
     stats = None
     if want_stats:
         nt = _n.call("spcl_conv_stat_rows", dt_code, N, H, W, 16, cout_s)
@@ -1014,6 +1015,27 @@ def _conv_image_acorr(x_store, dt_code, dtype, N, H, W, cin_s, cout_s, wp, want_
     _n.call("spcl_conv3x3_forward_image_acorr", _n.ptr(x_store), dt_code, N, H, W, cin_s, cout_s, _n.ptr(wp), _n.ptr(y),
             _n.ptr(stats), _n.ptr(acorr), _n.stream())
     return y, stats, acorr
+
+
+# A/B switch: 0 = the image block stores its first convolution's raw output (103 MB at 64 x 224^2: written once, read by the
+# second convolution's forward and by its backward) instead of forming it again per tile from the image in those two launches
+_BLOCK1_RECOMPUTE = os.environ.get("SPCL_BLOCK1_RECOMPUTE", "1") != "0"
+
+
+def _conv_from_image(image, y_image, dt_code, dtype, N, H, W, cout_s, wp_image, scale, shift, wp, want_stats):
+    """the image block's second convolution with its input relu(scale y1a + shift) formed per tile from the f32 image and the
+    first convolution's packed weights (spcl_conv3x3_forward_from_image; ``y_image``: the stored y1a is read instead, on the
+    same 14 x 14 tiles) -> (y, stats), one statistics row set per 14 x 14 tile"""
+    dev = image.device
+    y = torch.empty(N, H, W, cout_s, dtype=dtype, device=dev)
+    stats = None
+    if want_stats:
+        nt = N * (H // 14) * (W // 14)
+        stats = torch.empty(_n.call("spcl_bn_stats_elems", nt, cout_s), dtype=torch.float32, device=dev)
+        stats.ntiles = nt
+    _n.call("spcl_conv3x3_forward_from_image", _n.ptr(image), _n.ptr(y_image), dt_code, N, H, W, cout_s, _n.ptr(wp_image),
+            _n.ptr(scale), _n.ptr(shift), _n.ptr(wp), _n.ptr(y), _n.ptr(stats), _n.stream())
+    return y, stats
 
 
 def take_prepacked(w, dtc, H, W):
@@ -1464,12 +1486,16 @@ _CONV16_FUSED = os.environ.get("SPCL_CONV16_FUSED", "1") != "0"  # A/B switch: 0
 _CONV16_WGROWS = os.environ.get("SPCL_CONV16_WGROWS", "1") != "0"  # A/B switch: 0 = per-tile rows + the folding launch
 
 
-def _conv16_bwd_fused(dy, wp_t, y2, st2, image, dt_code, N, H, W, cin, cout, cs, sink, acorr=None):
+def _conv16_bwd_fused(dy, wp_t, y2, st2, image, dt_code, N, H, W, cin, cout, cs, sink, acorr=None, wp_image=None):
     """the image block's second conv, whole backward in one launch (csrc/conv16_bwd.hip): -> (dW or None when it went into
     a bucket slice, rows of the first conv's BatchNorm backward / weight gradient).  With ``acorr`` (the autocorrelation's
     partial rows) the rows come as ONE set per workgroup in the final kernel's layout (``rows.wg``) and the same launch
-    folds ``acorr`` to 16 rows (``rows.acorr16``): no per-tile rows, no folding launch; else per tile ([tiles][11][cs])."""
+    folds ``acorr`` to 16 rows (``rows.acorr16``): no per-tile rows, no folding launch; else per tile ([tiles][11][cs]).
+    ``y2`` None: the first conv's output was never stored -- the kernel forms it from ``image`` and ``wp_image``, that conv's
+    packed forward weights (spcl_conv16_bwd_fused_image)."""
     dev = dy.device
+    if y2 is None and wp_image is None:
+        raise RuntimeError("conv16 backward: neither the first convolution's output nor its packed weights")
     nsplit = _n.call("spcl_conv16_bwd_fused_splits", N, H, W)
     if acorr is not None:
         rows = torch.empty(11 * cs * nsplit, dtype=torch.float32, device=dev)
@@ -1482,14 +1508,15 @@ def _conv16_bwd_fused(dy, wp_t, y2, st2, image, dt_code, N, H, W, cin, cout, cs,
     dw = _grad_buffer(sink, (cout, cin, 3, 3), dev)
 
     def launch():
-        _n.call("spcl_conv16_bwd_fused", _n.ptr(dy), dt_code, N, H, W, _n.ptr(wp_t), _n.ptr(y2), _n.ptr(st2[2]),
+        _n.call("spcl_conv16_bwd_fused" if y2 is not None else "spcl_conv16_bwd_fused_image", _n.ptr(dy), dt_code, N, H, W,
+                _n.ptr(wp_t), _n.ptr(y2 if y2 is not None else wp_image), _n.ptr(st2[2]),
                 _n.ptr(st2[3]), _n.ptr(st2[0]), _n.ptr(image), _n.ptr(rows) if not rows.wg else None, _n.ptr(ws), _n.ptr(dw),
                 cin, cout, _n.ptr(rows) if rows.wg else None, _n.ptr(acorr), 0 if acorr is None else acorr.shape[0],
                 _n.ptr(rows.acorr16) if rows.wg else None, _n.stream())
 
     queue = sink_queue(sink)
     if queue is not None and _TAILS:
-        if queue.capture_tail(sink, (ws, dy, y2, image, rows), launch):
+        if queue.capture_tail(sink, (ws, dy, y2, image, rows, wp_image), launch):
             return None, rows
         return dw, rows
     launch()
@@ -1656,6 +1683,7 @@ class _ConvBlockFn(torch.autograd.Function):
         use_b = (acc_ok and not lazy and not ctx.up2 and getattr(cfg, "act_dst", None) is None
                  and sup(cout_s, cout_s, 1 if use_a else 2, 1))
         keep = []
+        recompute = False
         ctx.acc_bwd_a = ctx.acc_bwd_b = ctx.acc_rows_a = None
         if use_a:
             acc_a = bn_acc_block(cout_s, dev)
@@ -1666,7 +1694,15 @@ class _ConvBlockFn(torch.autograd.Function):
             if x2s is not None:
                 ya, sa = _conv_cat(xs, x2s, dtc, dtype, N, H, W, chalf, cout_s, wpa, cfg.training, *ctx.x2_coef)
             elif acorr_rows > 0:  # the image convolution leaves the autocorrelation rows of the image3 backward itself
-                ya, sa, ctx.acorr = _conv_image_acorr(xs, dtc, dtype, N, H, W, cin_s, cout_s, wpa, cfg.training, acorr_rows)
+                # ... and, where the second convolution and the block's backward can form its output again from the image,
+                # nothing else: ya is never stored.  That needs the rows form of BOTH BatchNorms and the one-pass backward:
+                # where Conv1.b's statistics go through an accumulator block (``use_b``: at most 4 096 tiles, N <= 16 at
+                # 224^2) the tensor is still stored, whatever spcl_block1_recompute_supported says about the kernels
+                recompute = (_BLOCK1_RECOMPUTE and _CONV16_FUSED and cfg.training and not use_b and cin == 1
+                             and cout == cout_s and ctx.needs_input_grad[4]
+                             and bool(_n.call("spcl_block1_recompute_supported", dtc, N, H, W, cin_s, cout_s)))
+                ya, sa, ctx.acorr = _conv_image_acorr(xs, dtc, dtype, N, H, W, cin_s, cout_s, wpa, cfg.training, acorr_rows,
+                                                      store=not recompute)
             else:
                 ya, sa = _conv(xs, dtc, dtype, N, H, W, cin_s, cin_k, cout_s, wpa, mode_a, None, None, cfg.training)
             sta = _bn_stats(sa, cfg, cout, cout_s, ga, ba, 0, dev)
@@ -1674,8 +1710,11 @@ class _ConvBlockFn(torch.autograd.Function):
             acc_b = bn_acc_block(cout_s, dev) if use_b else None
             yb, sb = _conv_acc(ya, dtc, dtype, N, H, W, cout_s, cout_s, wpb, bn_a if use_a else None,
                                None if use_a else sta[2], None if use_a else sta[3], acc_b, cfg.training)
+        elif recompute:
+            yb, sb = _conv_from_image(xs, None, dtc, dtype, N, H, W, cout_s, wpa, sta[2], sta[3], wpb, cfg.training)
         else:
             yb, sb = _conv(ya, dtc, dtype, N, H, W, cout_s, cout_s, cout_s, wpb, 1, sta[2], sta[3], cfg.training)
+        ctx.wpa_fwd = wpa if recompute else None  # (the backward forms ya from the image with them)
         if use_b:
             stb = torch.empty(4, cout_s, dtype=torch.float32, device=dev)  # written by the activation writer's first workgroup
             bn_b = _bn_acc_desc(acc_b, cfg, cout, cout_s, gb, bb, 1, count, stb, keep)
@@ -1839,11 +1878,14 @@ class _ConvBlockFn(torch.autograd.Function):
             wpb_t = _pack(wb, 1, dtc, dtype)
         image3 = ctx.acorr is not None
         # image block: this conv's weight gradient AND the sums the first conv's backward needs in one pass over dyb / ya
-        one_pass = (image3 and _CONV16_FUSED and ctx.needs_input_grad[4] and cout == cout_s
+        one_pass = (image3 and (_CONV16_FUSED or ya is None) and ctx.needs_input_grad[4] and cout == cout_s
                     and _n.call("spcl_conv16_bwd_fused_supported", dtc, N, H, W, cout_s, cout_s))
+        if ya is None and not one_pass:  # (the forward offered the recomputation where this holds: never a silent fallback)
+            raise RuntimeError("image block backward: the first convolution's output was not stored and the one-pass kernel "
+                               "that forms it again is not available")
         if one_pass:
             dwb, rows16 = _conv16_bwd_fused(dyb, wpb_t, ya, sta, xs, dtc, N, H, W, cout, cout, cout_s, sk[3],
-                                            acorr=ctx.acorr if _CONV16_WGROWS else None)
+                                            acorr=ctx.acorr if _CONV16_WGROWS else None, wp_image=ctx.wpa_fwd)
         else:
             dwb = _wgrad(ya, dyb, dtc, N, H, W, cout, cout_s, cout_s, cout, cout_s, 1, sta[2], sta[3], sk[3]) \
                 if ctx.needs_input_grad[4] else None
