@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 19
+#define SPCL_ABI_VERSION 20
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -115,6 +115,42 @@ int spcl_supcon_xpos_forward(const float* z1, const float* z2, const float* labe
                              float temperature, float* ws, float* out, void* stream);
 int spcl_supcon_xpos_backward(const float* z1, const float* z2, int n, int d, float temperature, const float* ws,
                               const float* grad_out, float* dz1, float* dz2, void* stream);
+
+/* Weighted supervised-contrastive losses (csrc/supcon_weighted.hip): replaces contrastyou/losses/contrast_loss.py:49-104
+ * (SupConLoss2, in / out mode), :144-181 (SupConLoss3, real-valued pos_weight) and :220-270 (SupConLoss4, block weights)
+ * and the autograd backward of those.  Over the 2n rows of cat(z1, z2), s_ij = z_i . z_j / t, pair weights P_ij >= 0 and
+ * a 0/1 denominator switch E_ij (both 0 on the diagonal):  D_i = sum_j E_ij exp(s_ij), W_i = sum_j P_ij,
+ *   in_mode == 0:  loss = -mean_i [ sum_j P_ij (s_ij - log D_i) / W_i ]
+ *   in_mode != 0:  loss = -mean_i [ log( sum_j P_ij exp(s_ij) / D_i ) / W_i ]
+ * P and E are read by index (u = i mod n, v = j mod n), never built as [2n,2n] matrices:
+ *   labels [n] f32 (blocks must be 0):  P = [labels_u == labels_v], E = 1  (contrast_loss.py:68-75; SimCLR, :76-80, is the
+ *     label vector 0 .. n-1)
+ *   labels NULL: bit 0 = w11 is block (1,1), bit 1 = w22 is block (2,2), bit 2 = w12 is BOTH blocks (1,2) and (2,1), not
+ *     transposed (:233-237); [n,n] f32 each, not assumed symmetric.  On a present block E = 1 and P = its entry w; on an
+ *     absent block P = E = 0.  mask_semantics != 0 reads w as P = [w == 1], E = [w == 0 or w == 1] (:62-66).
+ *     SupConLoss3's pos_weight.repeat(2, 2) (:152) is the same matrix in all three slots, blocks == 7.
+ * z1, z2 [n,d] f32 unit rows; n <= 4096, d <= 4096 (spcl_supcon_weighted_workspace_bytes returns 0 beyond).
+ * ws: workspace of that many bytes.  For 2n <= 64 and d <= 256 (one workgroup, one launch, exact-f32 MFMA) its first 2n*d
+ * floats are dLoss/dz (rows of z1, then of z2; pitch d) for a unit upstream gradient after the forward call, and the backward
+ * call is one scaling launch; above that S is formed in 64 x 64 tiles on the same MFMA, row kernels take the statistics, and
+ * dLoss/dS stays there ([2n,2n]) for the backward call's tiles.
+ * out [8] f32: out[0] = loss (NaN when a row has W_i = 0 in out mode, as the reference's arithmetic: it raises, :102-103,
+ * 179-180,268-269), out[1] = 1, out[2] = 1/2n, out[3] = max | |row| - 1 | (is_normalized, :20-22).  Sums in a fixed order. */
+size_t spcl_supcon_weighted_workspace_bytes(int n, int d);
+int spcl_supcon_weighted_forward(const float* z1, const float* z2, const float* labels, const float* w11,
+                                 const float* w22, const float* w12, int blocks, int mask_semantics, int in_mode, int n,
+                                 int d, float temperature, float* ws, float* out, void* stream);
+/* dz1, dz2 [n,d] f32 = grad_out[0] * dLoss/dz, from what the forward call left in ws (same z1, z2, n, d, temperature);
+ * above the one-workgroup sizes it writes its partial sums into a part of ws the forward call left free */
+int spcl_supcon_weighted_backward(const float* z1, const float* z2, int n, int d, float temperature, float* ws,
+                                  const float* grad_out, float* dz1, float* dz2, void* stream);
+/* the [2n,2n] hook taps as the reference stores them, BEFORE the diagonal is removed (contrast_loss.py:83-86,159-161,
+ * 247-250): sim_logits = S/t - max(S/t), sim_exp = exp(sim_logits), pos_weight = P, enable_mask = E (SupConLoss2's
+ * neg_mask is E - P).  Any of the four may be NULL.  Uses the last 2n floats of ws as scratch, nothing else of it. */
+int spcl_supcon_weighted_materialize(const float* z1, const float* z2, const float* labels, const float* w11,
+                                     const float* w22, const float* w12, int blocks, int mask_semantics, int n, int d,
+                                     float temperature, float* ws, float* sim_logits, float* sim_exp, float* pos_weight,
+                                     float* enable_mask, void* stream);
 
 /* ---------------------------------------------------------------- projector ------------------------------
  * Replaces contrastyou/projectors/heads.py:9-25,78-92 + nn.py:8-15,29-36,56-58:

@@ -17,6 +17,7 @@ __version__ = "0.1.0"
 _MIRRORED = {
     "contrastyou": "contrastyou",
     "contrastyou.losses": "contrastyou.losses",
+    "contrastyou.losses.contrast_loss": "contrastyou.losses.contrast_loss",
     "contrastyou.losses.contrast_loss3": "contrastyou.losses.contrast_loss3",
     "contrastyou.losses.iic_loss": "contrastyou.losses.iic_loss",
     "contrastyou.meters": "contrastyou.meters",

@@ -258,6 +258,93 @@ def supcon_loss_exclude_other_pos(z1, z2, labels=None, mask=None, *, t=0.07, out
     return _SupConXposFn.apply(z1, z2, labels, mask, float(t), out)
 
 
+class SupConWeightedState:
+    """Device-side results of one weighted-loss evaluation (kept for the lazily materialised taps)."""
+    __slots__ = ("n", "d", "t", "z1", "z2", "labels", "w11", "w22", "w12", "blocks", "mask_semantics", "ws", "out")
+
+
+_WEIGHTED_UNIT_ROWS, _WEIGHTED_UNIT_D = 64, 256  # up to here the forward leaves dLoss/dz at the start of ws (spcl_hip.h)
+
+
+class _SupConWeightedFn(torch.autograd.Function):
+    """SupConLoss2 / 3 / 4 of contrast_loss.py:34-270 (csrc/supcon_weighted.hip).  ``z2 is None``: z1 is the whole [2n, d]
+    projection (view 1 rows, then view 2 rows) and the gradient comes back as one [2n, d] tensor."""
+
+    @staticmethod
+    def forward(ctx, z1, z2, labels, w11, w22, w12, blocks, mask_semantics, in_mode, t, state):
+        stacked = z2 is None
+        _n.require_gpu(z1, z2, labels, w11, w22, w12)
+        z1c = z1.detach().contiguous().float()
+        if stacked:
+            assert z1c.dim() == 2 and z1c.shape[0] % 2 == 0, z1c.shape
+            n, d = z1c.shape[0] // 2, z1c.shape[1]
+            z1c, z2c = z1c[:n], z1c[n:]
+        else:
+            z2c = z2.detach().contiguous().float()
+            n, d = z1c.shape
+        nbytes = _n.call("spcl_supcon_weighted_workspace_bytes", n, d)
+        if nbytes == 0:
+            raise RuntimeError(f"supcon (weighted): unsupported shape n={n} d={d} (n <= 4096, d <= 4096)")
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=z1.device)
+        out = torch.empty(8, dtype=torch.float32, device=z1.device)
+        _n.call("spcl_supcon_weighted_forward", _n.ptr(z1c), _n.ptr(z2c), _n.ptr(labels), _n.ptr(w11), _n.ptr(w22),
+                _n.ptr(w12), blocks, int(mask_semantics), int(in_mode), n, d, c_float(t), _n.ptr(ws), _n.ptr(out),
+                _n.stream())
+        state.n, state.d, state.t, state.z1, state.z2 = n, d, t, z1c, z2c
+        state.labels, state.w11, state.w22, state.w12 = labels, w11, w22, w12
+        state.blocks, state.mask_semantics, state.ws, state.out = blocks, int(mask_semantics), ws, out
+        ctx.state = state
+        ctx.stacked = stacked
+        ctx.in_dtypes = (z1.dtype, z1.dtype if stacked else z2.dtype)
+        ctx.leaf_input = bool(z1.is_leaf or (z2 is not None and z2.is_leaf))
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        s = ctx.state
+        n, d = s.n, s.d
+        tail = (None,) * 9
+        if (2 * n <= _WEIGHTED_UNIT_ROWS and d <= _WEIGHTED_UNIT_D and is_unit_gradient(grad_out)
+                and all(dt == torch.float32 for dt in ctx.in_dtypes)):
+            # the forward already left dLoss/dz for a unit gradient at the start of its workspace: that block IS the gradient
+            dz = s.ws[:2 * n * d].view(2 * n, d)
+            if ctx.leaf_input:  # (a leaf keeps what it is handed as its .grad: it must own it)
+                dz = dz.clone()
+            return ((dz, None) if ctx.stacked else (dz[:n], dz[n:])) + tail
+        dz = torch.empty(2 * n, d, dtype=torch.float32, device=s.ws.device)
+        go = grad_out.detach().reshape(1).float().contiguous()
+        _n.call("spcl_supcon_weighted_backward", _n.ptr(s.z1), _n.ptr(s.z2), n, d, c_float(s.t), _n.ptr(s.ws), _n.ptr(go),
+                _n.ptr(dz[:n]), _n.ptr(dz[n:]), _n.stream())
+        if ctx.stacked:
+            return (dz.to(ctx.in_dtypes[0]), None) + tail
+        return (dz[:n].to(ctx.in_dtypes[0]), dz[n:].to(ctx.in_dtypes[1])) + tail
+
+
+def supcon_weighted_loss(z1, z2, *, labels=None, w11=None, w22=None, w12=None, mask_semantics=False, in_mode=False,
+                         t=0.07, state: SupConWeightedState = None):
+    """loss (0-dim tensor with grad_fn) of the (P, E) criterion of csrc/supcon_weighted.hip.  ``labels`` [n] float32, or up to
+    three contiguous float32 [n, n] blocks -- ``w11`` block (1,1), ``w22`` block (2,2), ``w12`` blocks (1,2) and (2,1): a
+    pair in a block that is not given has no weight and is not in the denominator.  ``z2=None``: z1 holds both halves
+    stacked (``stacked_halves``).  The weights receive no gradient."""
+    if state is None:
+        state = SupConWeightedState()
+    blocks = (1 if w11 is not None else 0) | (2 if w22 is not None else 0) | (4 if w12 is not None else 0)
+    return _SupConWeightedFn.apply(z1, z2, labels, w11, w22, w12, blocks, bool(mask_semantics), bool(in_mode), float(t),
+                                   state)
+
+
+def supcon_weighted_materialize(state: SupConWeightedState, want=("sim_logits", "sim_exp", "pos_weight", "enable_mask")):
+    n2 = 2 * state.n
+    dev = state.ws.device
+    bufs = {k: (torch.empty(n2, n2, dtype=torch.float32, device=dev) if k in want else None)
+            for k in ("sim_logits", "sim_exp", "pos_weight", "enable_mask")}
+    _n.call("spcl_supcon_weighted_materialize", _n.ptr(state.z1), _n.ptr(state.z2), _n.ptr(state.labels), _n.ptr(state.w11),
+            _n.ptr(state.w22), _n.ptr(state.w12), state.blocks, state.mask_semantics, state.n, state.d, c_float(state.t),
+            _n.ptr(state.ws), _n.ptr(bufs["sim_logits"]), _n.ptr(bufs["sim_exp"]), _n.ptr(bufs["pos_weight"]),
+            _n.ptr(bufs["enable_mask"]), _n.stream())
+    return bufs
+
+
 def stacked_halves(a: torch.Tensor, b: torch.Tensor):
     """the tensor whose first / second half of rows a and b are (``torch.chunk(z, 2)`` outputs), else None"""
     base = a._base
