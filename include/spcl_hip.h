@@ -954,7 +954,9 @@ int spcl_bnrelu_backward_rows_acc(const void* y, const void* dact, const void* d
  *                    columns s*K + k of dlx / dly are written, the others are left alone.
  *   spcl_consistency_softmax_mse: weight * mean((softmax(flip(a)) - softmax(b))^2) over [N][H][W][C] f32 class maps (C <= 16),
  *                    db = its gradient w.r.t. b for a unit upstream gradient (a gets none); ws:
- *                    spcl_consistency_workspace_bytes(N, H, W).  The loss is a fixed-order sum: deterministic. */
+ *                    spcl_consistency_workspace_bytes(N, H, W).  The loss is a fixed-order sum: deterministic.  It is
+ *                    spcl_mt_softmax_mse with teacher_mode = 1 (the same launch), and like it refuses N*H*W >= 2^31 (such
+ *                    sizes used to be accepted and overflowed the workgroup count). */
 size_t spcl_iic_joint_workspace_bytes(int S, int K, int pad);
 int spcl_iic_joint_forward(const float* lx, const float* ly, long ld, int N, int H, int W, int S, int K, int pad,
                            const uint8_t* flags_x, long long* jacc, void* stream);

@@ -1,5 +1,5 @@
 // IIC (invariant information clustering) criteria of the UDA-IIC baseline (semi_seg/hooks/discretemi.py,
-// contrastyou/losses/iic_loss.py) and the softmax-consistency criterion (semi_seg/hooks/consistency.py).
+// contrastyou/losses/iic_loss.py).
 //
 // Form (b) of the joint: the cluster heads' logits come from spcl_rows_linear_forward (all S subheads in one product, the
 // rows [N][H][W][ld] f32 with subhead s in columns s*K .. s*K+K-1); the kernels apply the grouped softmax as they stage a
@@ -282,93 +282,10 @@ __global__ void __launch_bounds__(256) iic_loss_kernel(const long long* __restri
     djout[off + e] = (float)((gg - gp) / z * coef);
   }
   // fixed-order sum of the partial losses by the last workgroup
-  const int nblk = gridDim.x * gridDim.y, bid = s * gridDim.x + t;
-  __shared__ unsigned int last;
-  if (tid == 0) {
-    partial[bid] = l;
-    __threadfence();
-    last = atomicAdd(ticket, 1u) == (unsigned)(nblk - 1);
-  }
-  __syncthreads();
-  if (last && tid == 0) {
-    __threadfence();
-    double tot = 0.0;
-    for (int b = 0; b < nblk; ++b) tot += *((volatile double*)partial + b);
-    const float lv = (float)(tot * coef);
-    loss[0] = lv;
-    if (nan_flag) nan_flag[0] = (dense && isnan(lv)) ? 1 : 0;
-    *ticket = 0u;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------- consistency
-// loss = weight * mean((softmax(flip(a)) - softmax(b))^2), gradient for b only (unit upstream gradient)
-__global__ void __launch_bounds__(256) consistency_kernel(const float* __restrict__ a, const float* __restrict__ b, int N, int C,
-                                                          int H, int W, const uint8_t* __restrict__ flags, float weight,
-                                                          float* __restrict__ loss, float* __restrict__ db,
-                                                          double* __restrict__ partial, unsigned int* __restrict__ ticket) {
-  __shared__ double sh[8];
-  const long M = (long)N * H * W;
-  const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const double inv = 1.0 / ((double)M * C);
-  double sq = 0.0;
-  if (pix < M) {
-    const int n = (int)(pix / ((long)H * W));
-    const int rem = (int)(pix - (long)n * H * W), u = rem / W, v = rem - u * W;
-    const uint8_t f = flags ? flags[n] : 0;
-    const float* ap = a + ((long)(n * H + flip_idx(u, H, f & 1)) * W + flip_idx(v, W, f & 2)) * C;
-    const float* bp = b + pix * C;
-    float pa[16], pb[16];
-    float ma = -INFINITY, mb = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) {
-        pa[k] = ap[k];
-        pb[k] = bp[k];
-        ma = fmaxf(ma, pa[k]);
-        mb = fmaxf(mb, pb[k]);
-      }
-    float za = 0.f, zb = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) {
-        pa[k] = expf(pa[k] - ma);
-        pb[k] = expf(pb[k] - mb);
-        za += pa[k];
-        zb += pb[k];
-      }
-    const float gs = (float)(2.0 * weight * inv);
-    float gk[16], sgp = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) {
-        pa[k] /= za;
-        pb[k] /= zb;
-        const float d = pb[k] - pa[k];
-        sq += (double)d * d;
-        gk[k] = gs * d;
-        sgp = fmaf(gk[k], pb[k], sgp);
-      }
-    float* dp = db + pix * C;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) dp[k] = pb[k] * (gk[k] - sgp);
-  }
-  sq = block_sum_d(sq, sh);
-  __shared__ unsigned int last;
-  if (threadIdx.x == 0) {
-    partial[blockIdx.x] = sq;
-    __threadfence();
-    last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (last && threadIdx.x == 0) {
-    __threadfence();
-    double tot = 0.0;
-    for (unsigned int q = 0; q < gridDim.x; ++q) tot += *((volatile double*)partial + q);
-    loss[0] = (float)(tot * inv * weight);
-    *ticket = 0u;
-  }
+  ordered_total(l, coef, loss, partial, ticket, s * gridDim.x + t, gridDim.x * gridDim.y, 0u, nullptr,
+                [nan_flag, dense](float lv, unsigned long long) {
+                  if (nan_flag) nan_flag[0] = (dense && isnan(lv)) ? 1 : 0;
+                });
 }
 
 template <int KP>
@@ -478,30 +395,5 @@ extern "C" int spcl_iic_loss(const long long* jacc, const float* jf32, int S, in
   SPCL_LAUNCH(iic_loss_kernel, dim3(T * T, S), dim3(256), lds, st, jacc, jf32, K, T, dense, scale, j_out, loss, dj, nan_flag,
               partial, ticket);
   SPCL_LAUNCH_CHECK("iic_loss_kernel");
-  return SPCL_OK;
-}
-
-extern "C" size_t spcl_consistency_workspace_bytes(int N, int H, int W) {
-  const long M = (long)N * H * W;
-  return (size_t)((M + 255) / 256) * sizeof(double) + 64;
-}
-
-extern "C" int spcl_consistency_softmax_mse(const float* a, const float* b, int N, int C, int H, int W, const uint8_t* flags_a,
-                                            float weight, float* loss, float* db, void* ws, size_t ws_bytes, void* stream) {
-  SPCL_CHECK_ARG(a && b && loss && db && ws, "spcl_consistency_softmax_mse: null pointer");
-  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C >= 1 && C <= 16, "spcl_consistency_softmax_mse: bad shape (C <= 16)");
-  SPCL_CHECK_ARG(ws_bytes >= spcl_consistency_workspace_bytes(N, H, W), "spcl_consistency_softmax_mse: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const long M = (long)N * H * W;
-  const int nblk = (int)((M + 255) / 256);
-  unsigned int* ticket = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double));
-  if (hipMemsetAsync(ticket, 0, sizeof(unsigned int), st) != hipSuccess) {
-    spcl::set_error("spcl_consistency_softmax_mse: memset failed");
-    return SPCL_ELAUNCH;
-  }
-  spcl::prof_cost(3.0 * M * C * 4, 20.0 * M * C);
-  SPCL_LAUNCH(consistency_kernel, dim3(nblk), dim3(256), 0, st, a, b, N, C, H, W, flags_a, weight, loss, db, (double*)ws,
-              ticket);
-  SPCL_LAUNCH_CHECK("consistency_kernel");
   return SPCL_OK;
 }

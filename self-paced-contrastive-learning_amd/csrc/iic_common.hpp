@@ -1,13 +1,13 @@
 // Device helpers shared by the IIC kernels (iic.hip, iic_patch.hip): the softmax applied as a logits row is staged, the
-// per-sample flip, the 32.32 fixed-point scale of the joint accumulators and the float64 workgroup reductions.
+// 32.32 fixed-point scale of the joint accumulators and the float64 workgroup minimum; the per-sample flip and the float64
+// workgroup sum come from pixel_criterion.hpp.
 #pragma once
 #include "common.hpp"
+#include "pixel_criterion.hpp"
 
 namespace {
 
 constexpr double kFix = 4294967296.0;  // 2^32
-
-__device__ __forceinline__ int flip_idx(int x, int n, bool f) { return f ? n - 1 - x : x; }
 
 // softmax of subhead s of the logits row at (n, u, v) into dst[KP] (pad entries 0); zeros when out of the image
 template <int KP>
@@ -37,15 +37,6 @@ __device__ __forceinline__ void stage_prob(const float* __restrict__ l, long ld,
   for (int k = 0; k < KP; ++k) dst[k] = x[k] * r;
 }
 
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-  return t;
-}
 __device__ __forceinline__ double block_min_d(double v, double* sh) {
   for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
   __syncthreads();

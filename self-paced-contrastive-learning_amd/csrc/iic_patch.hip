@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(kThreads) iic_patch_loss_kernel(const long lon
   }
   __syncthreads();
   if (last) {  // (uniform over the workgroup)
-    // 256 partials at a time into shared memory, added by one thread in index order (semi_reg.hip's ordered_total: a chain
+    // 256 partials at a time into shared memory, added by one thread in index order (pixel_criterion.hpp's ordered_total: a chain
     // of dependent global loads would cost more than the rest of the launch)
     __shared__ double stage[kThreads];
     __threadfence();

@@ -31,14 +31,16 @@
 //   spcl_mixup_kl_onehot: weight * KL_div(eps)(softmax(logits), lam * onehot(y) + (1 - lam) * onehot(y[index])) and its
 //                         gradient (mixup.py:31,66-75): the soft target is built per pixel from two labels, never stored.
 //
-// The criteria: one thread per pixel (C <= 16 channels in registers), per-workgroup double partials, the last workgroup
-// to take a ticket sums them in index order (fetched 256 at a time through shared memory) and resets the ticket: loss and
-// gradient are bitwise reproducible.
+// The criteria are pixel functors on the one skeleton of pixel_criterion.hpp (one thread per pixel, per-workgroup double
+// partials, summed in index order by the last workgroup): loss and gradient are bitwise reproducible.
+//   spcl_consistency_softmax_mse, spcl_mt_softmax_mse(teacher_mode = 1):  mt_mse<true> -- the same launch
+//   spcl_mt_softmax_mse(teacher_mode = 0):                                mt_mse<false>
+//   spcl_entropy_softmax:  entropy_term      spcl_ucmt_softmax_mse:  ucmt_mse<4> / ucmt_mse<0>
+//   spcl_mixup_kl_onehot:  mixup_kl
 #include "common.hpp"
+#include "pixel_criterion.hpp"
 
 namespace {
-
-__device__ __forceinline__ int flip_idx(int x, int n, bool f) { return f ? n - 1 - x : x; }
 
 // three f32 roundings, in the reference's order: t * alpha | + (1 - alpha) * s (one fused multiply-add, as torch's
 // add_(s, alpha=) computes it) | * (1 - decay).  DECAY = false leaves the last one out (no multiplication by 1.0).
@@ -77,101 +79,23 @@ __global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ t, 
   }
 }
 
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = 0.0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += sh[w];
-  return r;
-}
-
-// the workgroup's partial -> partial[blockIdx.x]; the last workgroup sums all of them in index order: its threads fetch 256
-// partials at a time into shared memory (one round trip to memory per 256 instead of one per partial), thread 0 adds them in
-// index order -- the same sequence of double additions as a plain loop over q.  With `counts`: the workgroup's integer `cnt`
-// -> counts[blockIdx.x], summed into total_count[0] the same way (an exact integer).  Workgroups of at most 256 threads.
-__device__ __forceinline__ void ordered_total(double v, double scale, float* __restrict__ loss, double* __restrict__ partial,
-                                              unsigned int* __restrict__ ticket, unsigned int cnt = 0u,
-                                              unsigned int* __restrict__ counts = nullptr,
-                                              unsigned long long* __restrict__ total_count = nullptr) {
-  __shared__ unsigned int last;
-  __shared__ double stage[256];
-  __shared__ unsigned int cstage[256];
-  if (threadIdx.x == 0) {
-    partial[blockIdx.x] = v;
-    if (counts) counts[blockIdx.x] = cnt;
-    __threadfence();
-    last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (last) {  // (uniform over the workgroup)
-    __threadfence();
-    double tot = 0.0;
-    unsigned long long n = 0ull;
-    for (unsigned int base = 0; base < gridDim.x; base += blockDim.x) {
-      const unsigned int q = base + threadIdx.x;
-      if (q < gridDim.x) {
-        stage[threadIdx.x] = *((volatile double*)partial + q);
-        if (counts) cstage[threadIdx.x] = *((volatile unsigned int*)counts + q);
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        const unsigned int m = gridDim.x - base < blockDim.x ? gridDim.x - base : blockDim.x;
-        for (unsigned int i = 0; i < m; ++i) tot += stage[i];
-        if (counts)
-          for (unsigned int i = 0; i < m; ++i) n += cstage[i];
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      loss[0] = (float)(tot * scale);
-      if (counts) total_count[0] = n;
-      *ticket = 0u;
-    }
-  }
-}
-
-// loss = weight * mean((flip(T) - softmax(b))^2); TSOFT: T = softmax(teacher), else T = teacher
+// weight * mean((flip(T) - softmax(b))^2) and its gradient w.r.t. b; TSOFT: T = softmax(a), else T = a.  gs = 2 weight / (M C).
 template <bool TSOFT>
-__global__ void __launch_bounds__(256) mt_mse_kernel(const float* __restrict__ a, const float* __restrict__ b, int N, int C,
-                                                     int H, int W, const uint8_t* __restrict__ flags, float weight,
-                                                     float* __restrict__ loss, float* __restrict__ db,
-                                                     double* __restrict__ partial, unsigned int* __restrict__ ticket) {
-  __shared__ double sh[8];
-  const long M = (long)N * H * W;
-  const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const double inv = 1.0 / ((double)M * C);
-  double sq = 0.0;
-  if (pix < M) {
-    const int n = (int)(pix / ((long)H * W));
-    const int rem = (int)(pix - (long)n * H * W), u = rem / W, v = rem - u * W;
-    const uint8_t f = flags ? flags[n] : 0;
-    const float* ap = a + ((long)(n * H + flip_idx(u, H, f & 1)) * W + flip_idx(v, W, f & 2)) * C;
-    const float* bp = b + pix * C;
-    float pa[16], pb[16];
-    float ma = -INFINITY, mb = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) {
-        pa[k] = ap[k];
-        pb[k] = bp[k];
-        ma = fmaxf(ma, pa[k]);
-        mb = fmaxf(mb, pb[k]);
-      }
-    float za = 0.f, zb = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) {
-        if (TSOFT) {
-          pa[k] = expf(pa[k] - ma);
-          za += pa[k];
-        }
-        pb[k] = expf(pb[k] - mb);
-        zb += pb[k];
-      }
-    const float gs = (float)(2.0 * weight * inv);
-    float gk[16], sgp = 0.f;
+struct mt_mse {
+  static constexpr bool kCounts = false;
+  const float* a;
+  const float* b;
+  int C, H, W;
+  const uint8_t* flags;
+  float gs;
+  float* db;
+  __device__ double operator()(long pix, bool&) const {
+    float pa[16], pb[16], g[16];
+    load_pixel<0>(a + flipped_pixel(pix, H, W, flags) * C, C, pa);
+    load_pixel<0>(b + pix * C, C, pb);
+    const float za = TSOFT ? softmax_numerators(pa, C) : 1.f, zb = softmax_numerators(pb, C);
+    double sq = 0.0;
+    float sgp = 0.f;
 #pragma unroll
     for (int k = 0; k < 16; ++k)
       if (k < C) {
@@ -179,46 +103,28 @@ __global__ void __launch_bounds__(256) mt_mse_kernel(const float* __restrict__ a
         pb[k] /= zb;
         const float d = pb[k] - pa[k];
         sq += (double)d * d;
-        gk[k] = gs * d;
-        sgp = fmaf(gk[k], pb[k], sgp);
+        g[k] = gs * d;
+        sgp = fmaf(g[k], pb[k], sgp);
       }
-    float* dp = db + pix * C;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) dp[k] = pb[k] * (gk[k] - sgp);
+    softmax_jacobian(pb, sgp, g, C);
+    store_pixel<0>(db + pix * C, C, g);
+    return sq;
   }
-  sq = block_sum_d(sq, sh);
-  ordered_total(sq, inv * weight, loss, partial, ticket);
-}
+};
 
-// loss = weight / M * sum_pixels -sum_c p_c log(p_c + eps);  d/dx_k = p_k (g_k - sum_c p_c g_c),
-// g_c = -(log(p_c + eps) + p_c / (p_c + eps)) * weight / M
-__global__ void __launch_bounds__(256) entropy_kernel(const float* __restrict__ x, long M, int C, float eps, float weight,
-                                                      float* __restrict__ loss, float* __restrict__ dx,
-                                                      double* __restrict__ partial, unsigned int* __restrict__ ticket) {
-  __shared__ double sh[8];
-  const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const double inv = 1.0 / (double)M;
-  double ent = 0.0;
-  if (pix < M) {
-    const float* xp = x + pix * C;
-    float p[16];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) {
-        p[k] = xp[k];
-        m = fmaxf(m, p[k]);
-      }
-    float z = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) {
-        p[k] = expf(p[k] - m);
-        z += p[k];
-      }
-    const float gs = (float)((double)weight * inv);
-    float g[16], sgp = 0.f, e = 0.f;
+// weight / M * sum_pixels -sum_c p_c log(p_c + eps);  d/dx_k = p_k (g_k - sum_c p_c g_c),
+// g_c = -(log(p_c + eps) + p_c / (p_c + eps)) * gs, gs = weight / M
+struct entropy_term {
+  static constexpr bool kCounts = false;
+  const float* x;
+  int C;
+  float eps, gs;
+  float* dx;
+  __device__ double operator()(long pix, bool&) const {
+    float p[16], g[16];
+    load_pixel<0>(x + pix * C, C, p);
+    const float z = softmax_numerators(p, C);
+    float sgp = 0.f, e = 0.f;
 #pragma unroll
     for (int k = 0; k < 16; ++k)
       if (k < C) {
@@ -229,58 +135,38 @@ __global__ void __launch_bounds__(256) entropy_kernel(const float* __restrict__ 
         g[k] = -(lq + p[k] / q) * gs;
         sgp = fmaf(g[k], p[k], sgp);
       }
-    ent = -(double)e;
-    float* dp = dx + pix * C;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) dp[k] = p[k] * (g[k] - sgp);
+    softmax_jacobian(p, sgp, g, C);
+    store_pixel<0>(dx + pix * C, C, g);
+    return -(double)e;
   }
-  ent = block_sum_d(ent, sh);
-  ordered_total(ent, inv * weight, loss, partial, ticket);
-}
+};
 
 // the K noisy teacher maps of spcl_ucmt_softmax_mse, by value in the kernel's argument block
 struct ucmt_noisy {
   const float* p[16];
 };
 
-// CT channels of one pixel -> v[0 .. CT); CT == 4: one 16-byte access (the caller checked the alignment), CT == 0: C of them
-template <int CT>
-__device__ __forceinline__ void load_pixel(const float* __restrict__ p, int C, float (&v)[16]) {
-  if (CT == 4) {
-    const f32x4 x = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = x[k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) v[k] = p[k];
-  }
-}
-
-// loss = weight / (M C) * sum_pixels m * sum_c (softmax(b) - softmax(flip(a)))^2, m = (u <= threshold),
+// weight / (M C) * sum_pixels m * sum_c (softmax(b) - softmax(flip(a)))^2, m = (u <= threshold),
 // u = -sum_c q_c log(q_c + eps) / log(C), q = softmax(flip((noisy[0] + ... + noisy[K-1]) / K)); d/db_k = m * the gradient of
-// mt_mse_kernel<true>.  CT = 4: C == 4 and every map 16-byte aligned (vector accesses); CT = 0: any C <= 16.
+// mt_mse<true>, gs = 2 weight / (M C).  CT = 4: C == 4 and every map 16-byte aligned (vector accesses); CT = 0: any C <= 16.
+// A kept pixel restates mt_mse<true>'s lines instead of sharing them: in the straight-line code of CT = 4 the compiler fuses
+// gs * d - sgp into one multiply-add (one rounding less than mt_mse<true>, whose per-channel branches keep the two apart), so
+// the two gradients are not the same bits, and each entry keeps the bits it has always returned.
 template <int CT>
-__global__ void __launch_bounds__(256) ucmt_mse_kernel(const float* __restrict__ a, const ucmt_noisy noisy, int K,
-                                                       const float* __restrict__ b, int N, int C, int H, int W,
-                                                       const uint8_t* __restrict__ flags, float threshold, float eps,
-                                                       float weight, float* __restrict__ loss, float* __restrict__ db,
-                                                       unsigned long long* __restrict__ kept, uint8_t* __restrict__ mask,
-                                                       double* __restrict__ partial, unsigned int* __restrict__ counts,
-                                                       unsigned int* __restrict__ ticket) {
-  __shared__ double sh[8];
-  const int CC = CT ? CT : C;
-  const long M = (long)N * H * W;
-  const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const double inv = 1.0 / ((double)M * CC);
-  double sq = 0.0;
-  bool keep = false;
-  if (pix < M) {
-    const int n = (int)(pix / ((long)H * W));
-    const int rem = (int)(pix - (long)n * H * W), u = rem / W, v = rem - u * W;
-    const uint8_t f = flags ? flags[n] : 0;
-    const long aoff = ((long)(n * H + flip_idx(u, H, f & 1)) * W + flip_idx(v, W, f & 2)) * CC;
+struct ucmt_mse {
+  static constexpr bool kCounts = true;
+  const float* a;
+  ucmt_noisy noisy;
+  int K;
+  const float* b;
+  int C, H, W;
+  const uint8_t* flags;
+  float threshold, eps, gs;
+  float* db;
+  uint8_t* mask;
+  __device__ double operator()(long pix, bool& keep) const {
+    const int CC = CT ? CT : C;
+    const long aoff = flipped_pixel(pix, H, W, flags) * CC;
     {  // the mask: the f32 sum of the K maps in list order, one division, softmax, normalised entropy
       float avg[16], x[16];
       load_pixel<CT>(noisy.p[0] + aoff, CC, avg);
@@ -293,20 +179,10 @@ __global__ void __launch_bounds__(256) ucmt_mse_kernel(const float* __restrict__
           if (k < CC) avg[k] += x[k];
       }
       const float fk = (float)K;
-      float mq = -INFINITY;
 #pragma unroll
       for (int k = 0; k < 16; ++k)
-        if (k < CC) {
-          avg[k] = avg[k] / fk;
-          mq = fmaxf(mq, avg[k]);
-        }
-      float zq = 0.f;
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (k < CC) {
-          avg[k] = expf(avg[k] - mq);
-          zq += avg[k];
-        }
+        if (k < CC) avg[k] = avg[k] / fk;
+      const float zq = softmax_numerators(avg, CC);
       float e = 0.f;
 #pragma unroll
       for (int k = 0; k < 16; ++k)
@@ -318,6 +194,7 @@ __global__ void __launch_bounds__(256) ucmt_mse_kernel(const float* __restrict__
       keep = unc <= threshold;  // (a NaN entropy keeps nothing, as torch's comparison)
     }
     if (mask) mask[pix] = keep ? 1 : 0;
+    double sq = 0.0;
     float g[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) g[k] = 0.f;
@@ -325,23 +202,7 @@ __global__ void __launch_bounds__(256) ucmt_mse_kernel(const float* __restrict__
       float pa[16], pb[16];
       load_pixel<CT>(a + aoff, CC, pa);
       load_pixel<CT>(b + pix * CC, CC, pb);
-      float ma = -INFINITY, mb = -INFINITY;
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (k < CC) {
-          ma = fmaxf(ma, pa[k]);
-          mb = fmaxf(mb, pb[k]);
-        }
-      float za = 0.f, zb = 0.f;
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (k < CC) {
-          pa[k] = expf(pa[k] - ma);
-          za += pa[k];
-          pb[k] = expf(pb[k] - mb);
-          zb += pb[k];
-        }
-      const float gs = (float)(2.0 * weight * inv);
+      const float za = softmax_numerators(pa, CC), zb = softmax_numerators(pb, CC);
       float sgp = 0.f;
 #pragma unroll
       for (int k = 0; k < 16; ++k)
@@ -353,26 +214,12 @@ __global__ void __launch_bounds__(256) ucmt_mse_kernel(const float* __restrict__
           g[k] = gs * d;
           sgp = fmaf(g[k], pb[k], sgp);
         }
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (k < CC) g[k] = pb[k] * (g[k] - sgp);
+      softmax_jacobian(pb, sgp, g, CC);
     }
-    float* dp = db + pix * CC;  // exact zeros where the pixel is masked out
-    if (CT == 4) {
-      f32x4 o;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = g[k];
-      *reinterpret_cast<f32x4*>(dp) = o;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (k < CC) dp[k] = g[k];
-    }
+    store_pixel<CT>(db + pix * CC, CC, g);  // exact zeros where the pixel is masked out
+    return sq;
   }
-  const unsigned int cnt = (unsigned int)block_sum_d(keep ? 1.0 : 0.0, sh);  // (at most 256: exact)
-  sq = block_sum_d(sq, sh);
-  ordered_total(sq, inv * weight, loss, partial, ticket, cnt, counts, kept);
-}
+};
 
 // sample n of the virtual concatenation (a, b) of two batches of B samples, per elements each
 template <typename T>
@@ -424,40 +271,24 @@ __global__ void __launch_bounds__(256) mixup_images_kernel(const float* __restri
 // loss = weight / M * sum_pixels sum_c -t_c log((p_c + eps) / (t_c + eps)), t_c = (c == la ? lam : 0) + (c == lb ? oml : 0) with
 // la the pixel's own label and lb the label of the same pixel in sample index[n];  d/dx_k = p_k (g_k - sum_c g_c p_c),
 // g_c = -(weight / M) t_c / (p_c + eps), evaluated as -(weight / M) (t_k r_k - p_k sum_c t_c r_c) with r_c = p_c / (p_c + eps)
-// <= 1 (the same value; no quotient by a vanishing p_c + eps is ever formed).  Labels are compared with c only.
-__global__ void __launch_bounds__(256) mixup_kl_kernel(const float* __restrict__ x, const int64_t* __restrict__ ya,
-                                                       const int64_t* __restrict__ yb, const int* __restrict__ index, int B,
-                                                       int HW, int C, float lam, float oml, float eps, float weight,
-                                                       float* __restrict__ loss, float* __restrict__ dx,
-                                                       double* __restrict__ partial, unsigned int* __restrict__ ticket) {
-  __shared__ double sh[8];
-  const int N2 = 2 * B;
-  const long M = (long)N2 * HW;
-  const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const double inv = 1.0 / (double)M;
-  double kl = 0.0;
-  if (pix < M) {
+// <= 1 (the same value; no quotient by a vanishing p_c + eps is ever formed).  Labels are compared with c only.  gs = weight / M.
+struct mixup_kl {
+  static constexpr bool kCounts = false;
+  const float* x;
+  const int64_t* ya;
+  const int64_t* yb;
+  const int* index;
+  int B, HW, C;
+  float lam, oml, eps, gs;
+  float* dx;
+  __device__ double operator()(long pix, bool&) const {
     const int n = (int)(pix / HW), rem = (int)(pix - (long)n * HW);
     const long la = cat_sample(ya, yb, n, B, (size_t)HW)[rem];
-    const long lb = cat_sample(ya, yb, mix_partner(index, n, N2), B, (size_t)HW)[rem];
-    const float* xp = x + pix * C;
-    float p[16];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) {
-        p[k] = xp[k];
-        m = fmaxf(m, p[k]);
-      }
-    float z = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) {
-        p[k] = expf(p[k] - m);
-        z += p[k];
-      }
-    const float gs = (float)((double)weight * inv);
-    float tr[16], str = 0.f, e = 0.f;
+    const long lb = cat_sample(ya, yb, mix_partner(index, n, 2 * B), B, (size_t)HW)[rem];
+    float p[16], tr[16];
+    load_pixel<0>(x + pix * C, C, p);
+    const float z = softmax_numerators(p, C);
+    float str = 0.f, e = 0.f;
 #pragma unroll
     for (int k = 0; k < 16; ++k)
       if (k < C) {
@@ -471,17 +302,13 @@ __global__ void __launch_bounds__(256) mixup_kl_kernel(const float* __restrict__
           str += tr[k];
         }
       }
-    kl = -(double)e;
     float* dp = dx + pix * C;
 #pragma unroll
     for (int k = 0; k < 16; ++k)
       if (k < C) dp[k] = -gs * (tr[k] - p[k] * str);
+    return -(double)e;
   }
-  kl = block_sum_d(kl, sh);
-  ordered_total(kl, inv * weight, loss, partial, ticket);
-}
-
-size_t pixel_workspace_bytes(long M) { return (size_t)((M + 255) / 256) * sizeof(double) + 64; }
+};
 
 template <bool DECAY>
 void launch_ema(float* t, const float* s, size_t head, size_t n4, size_t n, float alpha, float oma, float keep, bool svec,
@@ -517,34 +344,38 @@ extern "C" int spcl_ema_update(float* teacher, const float* student, size_t n, d
   return SPCL_OK;
 }
 
+extern "C" size_t spcl_consistency_workspace_bytes(int N, int H, int W) { return pixel_workspace_bytes((long)N * H * W); }
+
+// mean teacher with a soft-maxed teacher under its older name: the same launch
+extern "C" int spcl_consistency_softmax_mse(const float* a, const float* b, int N, int C, int H, int W, const uint8_t* flags_a,
+                                            float weight, float* loss, float* db, void* ws, size_t ws_bytes, void* stream) {
+  SPCL_CHECK_ARG(a && b && loss && db && ws, "spcl_consistency_softmax_mse: null pointer");
+  pixel_launch p;
+  if (int rc = pixel_prepare("spcl_consistency_softmax_mse", "C <= 16", N, C, H, W, ws, ws_bytes, false, stream, &p)) return rc;
+  const double inv = 1.0 / ((double)p.M * C);
+  spcl::prof_cost(3.0 * p.M * C * 4, 20.0 * p.M * C);
+  return launch_pixel_criterion("spcl_consistency_softmax_mse", mt_mse<true>{a, b, C, H, W, flags_a, (float)(2.0 * weight * inv), db},
+                                p, inv * weight, loss);
+}
+
 extern "C" size_t spcl_mt_softmax_mse_workspace_bytes(int N, int H, int W) { return pixel_workspace_bytes((long)N * H * W); }
 
 extern "C" int spcl_mt_softmax_mse(const float* teacher, const float* student_logits, int N, int C, int H, int W,
                                    const uint8_t* flags_teacher, int teacher_mode, float weight, float* loss, float* dstudent,
                                    void* ws, size_t ws_bytes, void* stream) {
   SPCL_CHECK_ARG(teacher && student_logits && loss && dstudent && ws, "spcl_mt_softmax_mse: null pointer");
-  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C >= 1 && C <= 16, "spcl_mt_softmax_mse: bad shape (C <= 16)");
-  SPCL_CHECK_ARG((long)N * H * W < (1L << 31), "spcl_mt_softmax_mse: too many pixels");
   SPCL_CHECK_ARG(teacher_mode == 0 || teacher_mode == 1, "spcl_mt_softmax_mse: teacher_mode %d is neither 0 (raw) nor 1 (softmax)",
                  teacher_mode);
-  SPCL_CHECK_ARG(ws_bytes >= spcl_mt_softmax_mse_workspace_bytes(N, H, W), "spcl_mt_softmax_mse: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const long M = (long)N * H * W;
-  const int nblk = (int)((M + 255) / 256);
-  unsigned int* ticket = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double));
-  if (hipMemsetAsync(ticket, 0, sizeof(unsigned int), st) != hipSuccess) {
-    spcl::set_error("spcl_mt_softmax_mse: memset failed");
-    return SPCL_ELAUNCH;
-  }
-  spcl::prof_cost(3.0 * M * C * 4, 20.0 * M * C);
+  pixel_launch p;
+  if (int rc = pixel_prepare("spcl_mt_softmax_mse", "C <= 16", N, C, H, W, ws, ws_bytes, false, stream, &p)) return rc;
+  const double inv = 1.0 / ((double)p.M * C);
+  const float gs = (float)(2.0 * weight * inv);
+  spcl::prof_cost(3.0 * p.M * C * 4, 20.0 * p.M * C);
   if (teacher_mode == 1)
-    SPCL_LAUNCH(mt_mse_kernel<true>, dim3(nblk), dim3(256), 0, st, teacher, student_logits, N, C, H, W, flags_teacher, weight,
-                loss, dstudent, (double*)ws, ticket);
-  else
-    SPCL_LAUNCH(mt_mse_kernel<false>, dim3(nblk), dim3(256), 0, st, teacher, student_logits, N, C, H, W, flags_teacher, weight,
-                loss, dstudent, (double*)ws, ticket);
-  SPCL_LAUNCH_CHECK("mt_mse_kernel");
-  return SPCL_OK;
+    return launch_pixel_criterion("spcl_mt_softmax_mse", mt_mse<true>{teacher, student_logits, C, H, W, flags_teacher, gs, dstudent},
+                                  p, inv * weight, loss);
+  return launch_pixel_criterion("spcl_mt_softmax_mse", mt_mse<false>{teacher, student_logits, C, H, W, flags_teacher, gs, dstudent},
+                                p, inv * weight, loss);
 }
 
 extern "C" size_t spcl_entropy_softmax_workspace_bytes(int N, int H, int W) { return pixel_workspace_bytes((long)N * H * W); }
@@ -552,36 +383,22 @@ extern "C" size_t spcl_entropy_softmax_workspace_bytes(int N, int H, int W) { re
 extern "C" int spcl_entropy_softmax(const float* logits, int N, int C, int H, int W, float eps, float weight, float* loss,
                                     float* dlogits, void* ws, size_t ws_bytes, void* stream) {
   SPCL_CHECK_ARG(logits && loss && dlogits && ws, "spcl_entropy_softmax: null pointer");
-  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C >= 1 && C <= 16, "spcl_entropy_softmax: bad shape (C <= 16)");
-  SPCL_CHECK_ARG((long)N * H * W < (1L << 31), "spcl_entropy_softmax: too many pixels");
   SPCL_CHECK_ARG(eps >= 0.f, "spcl_entropy_softmax: negative eps");
-  SPCL_CHECK_ARG(ws_bytes >= spcl_entropy_softmax_workspace_bytes(N, H, W), "spcl_entropy_softmax: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const long M = (long)N * H * W;
-  const int nblk = (int)((M + 255) / 256);
-  unsigned int* ticket = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double));
-  if (hipMemsetAsync(ticket, 0, sizeof(unsigned int), st) != hipSuccess) {
-    spcl::set_error("spcl_entropy_softmax: memset failed");
-    return SPCL_ELAUNCH;
-  }
-  spcl::prof_cost(2.0 * M * C * 4, 30.0 * M * C);
-  SPCL_LAUNCH(entropy_kernel, dim3(nblk), dim3(256), 0, st, logits, M, C, eps, weight, loss, dlogits, (double*)ws, ticket);
-  SPCL_LAUNCH_CHECK("entropy_kernel");
-  return SPCL_OK;
+  pixel_launch p;
+  if (int rc = pixel_prepare("spcl_entropy_softmax", "C <= 16", N, C, H, W, ws, ws_bytes, false, stream, &p)) return rc;
+  const double inv = 1.0 / (double)p.M;
+  spcl::prof_cost(2.0 * p.M * C * 4, 30.0 * p.M * C);
+  return launch_pixel_criterion("spcl_entropy_softmax", entropy_term{logits, C, eps, (float)((double)weight * inv), dlogits}, p,
+                                inv * weight, loss);
 }
 
-// [partials: nblk doubles][ticket, 64 bytes][counts: nblk unsigned ints]
-extern "C" size_t spcl_ucmt_workspace_bytes(int N, int H, int W) {
-  const long M = (long)N * H * W;
-  return pixel_workspace_bytes(M) + (size_t)((M + 255) / 256) * sizeof(unsigned int);
-}
+extern "C" size_t spcl_ucmt_workspace_bytes(int N, int H, int W) { return pixel_workspace_bytes((long)N * H * W, true); }
 
 extern "C" int spcl_ucmt_softmax_mse(const float* teacher, const float* const* noisy, int K, const float* student_logits, int N,
                                      int C, int H, int W, const uint8_t* flags_teacher, float threshold, float eps, float weight,
                                      float* loss, float* dstudent, unsigned long long* kept, uint8_t* mask, void* ws,
                                      size_t ws_bytes, void* stream) {
   SPCL_CHECK_ARG(K >= 1 && K <= 16, "spcl_ucmt_softmax_mse: K = %d noisy maps (1 <= K <= 16)", K);
-  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C >= 1 && C <= 16, "spcl_ucmt_softmax_mse: bad shape (C <= 16)");
   SPCL_CHECK_ARG(teacher && noisy && student_logits && loss && dstudent && kept && ws, "spcl_ucmt_softmax_mse: null pointer");
   ucmt_noisy maps{};
   bool vec = C == 4 && ((uintptr_t)teacher | (uintptr_t)student_logits | (uintptr_t)dstudent) % 16 == 0;
@@ -590,27 +407,19 @@ extern "C" int spcl_ucmt_softmax_mse(const float* teacher, const float* const* n
     maps.p[j] = noisy[j];
     vec = vec && (uintptr_t)noisy[j] % 16 == 0;
   }
-  SPCL_CHECK_ARG((long)N * H * W < (1L << 31), "spcl_ucmt_softmax_mse: too many pixels");
   SPCL_CHECK_ARG(eps >= 0.f, "spcl_ucmt_softmax_mse: negative eps");
-  SPCL_CHECK_ARG(ws_bytes >= spcl_ucmt_workspace_bytes(N, H, W), "spcl_ucmt_softmax_mse: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const long M = (long)N * H * W;
-  const int nblk = (int)((M + 255) / 256);
-  unsigned int* ticket = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double));
-  unsigned int* counts = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double) + 64);
-  if (hipMemsetAsync(ticket, 0, sizeof(unsigned int), st) != hipSuccess) {
-    spcl::set_error("spcl_ucmt_softmax_mse: memset failed");
-    return SPCL_ELAUNCH;
-  }
-  spcl::prof_cost((double)(K + 3) * M * C * 4 + (mask ? (double)M : 0.0), (20.0 + 2.0 * K + 20.0) * M * C);
+  pixel_launch p;
+  if (int rc = pixel_prepare("spcl_ucmt_softmax_mse", "C <= 16", N, C, H, W, ws, ws_bytes, true, stream, &p)) return rc;
+  const double inv = 1.0 / ((double)p.M * C);
+  const float gs = (float)(2.0 * weight * inv);
+  spcl::prof_cost((double)(K + 3) * p.M * C * 4 + (mask ? (double)p.M : 0.0), (20.0 + 2.0 * K + 20.0) * p.M * C);
   if (vec)
-    SPCL_LAUNCH(ucmt_mse_kernel<4>, dim3(nblk), dim3(256), 0, st, teacher, maps, K, student_logits, N, C, H, W, flags_teacher,
-                threshold, eps, weight, loss, dstudent, kept, mask, (double*)ws, counts, ticket);
-  else
-    SPCL_LAUNCH(ucmt_mse_kernel<0>, dim3(nblk), dim3(256), 0, st, teacher, maps, K, student_logits, N, C, H, W, flags_teacher,
-                threshold, eps, weight, loss, dstudent, kept, mask, (double*)ws, counts, ticket);
-  SPCL_LAUNCH_CHECK("ucmt_mse_kernel");
-  return SPCL_OK;
+    return launch_pixel_criterion("spcl_ucmt_softmax_mse", ucmt_mse<4>{teacher, maps, K, student_logits, C, H, W, flags_teacher,
+                                                                        threshold, eps, gs, dstudent, mask},
+                                  p, inv * weight, loss, kept);
+  return launch_pixel_criterion("spcl_ucmt_softmax_mse", ucmt_mse<0>{teacher, maps, K, student_logits, C, H, W, flags_teacher,
+                                                                      threshold, eps, gs, dstudent, mask},
+                                p, inv * weight, loss, kept);
 }
 
 extern "C" int spcl_mixup_images(const float* image, const float* image_tf, const int* index, int N2, size_t per_sample,
@@ -643,22 +452,13 @@ extern "C" int spcl_mixup_kl_onehot(const float* logits, const int64_t* target, 
                                     int N2, int C, int H, int W, float lam, float oml, float eps, float weight, float* loss,
                                     float* dlogits, void* ws, size_t ws_bytes, void* stream) {
   SPCL_CHECK_ARG(logits && target && target_tf && index && loss && dlogits && ws, "spcl_mixup_kl_onehot: null pointer");
-  SPCL_CHECK_ARG(N2 > 0 && N2 % 2 == 0 && H > 0 && W > 0 && C >= 1 && C <= 16,
-                 "spcl_mixup_kl_onehot: bad shape (N2 = 2 B, C <= 16)");
-  SPCL_CHECK_ARG((long)N2 * H * W < (1L << 31), "spcl_mixup_kl_onehot: too many pixels");
+  SPCL_CHECK_ARG(N2 % 2 == 0, "spcl_mixup_kl_onehot: bad shape (N2 = 2 B, C <= 16)");
   SPCL_CHECK_ARG(eps >= 0.f, "spcl_mixup_kl_onehot: negative eps");
-  SPCL_CHECK_ARG(ws_bytes >= spcl_mixup_kl_workspace_bytes(N2, H, W), "spcl_mixup_kl_onehot: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const long M = (long)N2 * H * W;
-  const int nblk = (int)((M + 255) / 256);
-  unsigned int* ticket = (unsigned int*)((char*)ws + (size_t)nblk * sizeof(double));
-  if (hipMemsetAsync(ticket, 0, sizeof(unsigned int), st) != hipSuccess) {
-    spcl::set_error("spcl_mixup_kl_onehot: memset failed");
-    return SPCL_ELAUNCH;
-  }
-  spcl::prof_cost(2.0 * M * C * 4 + 16.0 * M, 30.0 * M * C);
-  SPCL_LAUNCH(mixup_kl_kernel, dim3(nblk), dim3(256), 0, st, logits, target, target_tf, index, N2 / 2, H * W, C, lam, oml, eps,
-              weight, loss, dlogits, (double*)ws, ticket);
-  SPCL_LAUNCH_CHECK("mixup_kl_kernel");
-  return SPCL_OK;
+  pixel_launch p;
+  if (int rc = pixel_prepare("spcl_mixup_kl_onehot", "N2 = 2 B, C <= 16", N2, C, H, W, ws, ws_bytes, false, stream, &p)) return rc;
+  const double inv = 1.0 / (double)p.M;
+  spcl::prof_cost(2.0 * p.M * C * 4 + 16.0 * p.M, 30.0 * p.M * C);
+  return launch_pixel_criterion("spcl_mixup_kl_onehot", mixup_kl{logits, target, target_tf, index, N2 / 2, H * W, C, lam, oml, eps,
+                                                                 (float)((double)weight * inv), dlogits},
+                                p, inv * weight, loss);
 }

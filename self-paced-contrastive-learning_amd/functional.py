@@ -2868,38 +2868,53 @@ def iic_patch_loss(lx, ly, *, padding, patch_size, scale=1.0, flags=None, out=No
     return _IICPatchLossFn.apply(lx, ly, flags, int(padding), int(patch_size), float(scale), [] if out is None else out)
 
 
-class _ConsistencyFn(torch.autograd.Function):
-    """``weight * MSELoss(softmax(flip(a)).detach(), softmax(b))`` in one launch; the gradient w.r.t. ``b`` for a unit upstream
-    gradient is written by the same launch (``a`` gets none: the reference detaches it)."""
+class _PixelCriterionFn(torch.autograd.Function):
+    """A fused per-pixel criterion (csrc/pixel_criterion.hpp): ``launch()`` checks its arguments, makes the one library call
+    on detached channels-last storage and returns the loss and the gradient map [N, H, W, C] w.r.t. ``x`` for a unit upstream
+    gradient; ``x`` is the one input that gets a gradient."""
 
     @staticmethod
-    def forward(ctx, a, b, flags, weight):
+    def forward(ctx, x, launch):
+        loss, grad = launch()
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        if is_unit_gradient(g):
+            return grad.permute(0, 3, 1, 2), None
+        return (grad * g.detach().float()).permute(0, 3, 1, 2), None
+
+
+_MixupKLFn = _PixelCriterionFn  # (the name tests/test_gpu_mixup_kernels.py drives ``backward`` under)
+
+
+def _pixel_criterion_buffers(storage, workspace_entry):
+    """(loss, gradient map, workspace) of a criterion over the [N, H, W, C] ``storage``"""
+    N, H, W, _ = storage.shape
+    dev = storage.device
+    return (torch.empty((), dtype=torch.float32, device=dev), torch.empty_like(storage),
+            torch.empty(_n.call(workspace_entry, N, H, W), dtype=torch.uint8, device=dev))
+
+
+def consistency_softmax_mse(a, b, weight=1.0, flags=None):
+    """consistency.py:30-35: ``weight * mse(softmax(flip(a)).detach(), softmax(b))`` of logical [N, C, H, W] logits"""
+    weight = float(weight)
+
+    def launch():
         _n.require_gpu(a, b)
         as_, bs = _class_map_storage(a.detach()), _class_map_storage(b.detach())
         if as_.shape != bs.shape:
             raise AssertionError(f"class maps {tuple(as_.shape)} / {tuple(bs.shape)} differ")
         N, H, W, C = bs.shape
-        dev = bs.device
-        fl = _flip_flags_arg(flags, N, dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        db = torch.empty_like(bs)
-        ws = torch.empty(_n.call("spcl_consistency_workspace_bytes", N, H, W), dtype=torch.uint8, device=dev)
+        fl = _flip_flags_arg(flags, N, bs.device)
+        loss, db, ws = _pixel_criterion_buffers(bs, "spcl_consistency_workspace_bytes")
         _n.call("spcl_consistency_softmax_mse", _n.ptr(as_), _n.ptr(bs), N, C, H, W, _n.ptr(fl), c_float(weight),
                 _n.ptr(loss), _n.ptr(db), _n.ptr(ws), ws.numel(), _n.stream())
-        ctx.save_for_backward(db)
-        return loss
+        return loss, db
 
-    @staticmethod
-    def backward(ctx, g):
-        (db,) = ctx.saved_tensors
-        if is_unit_gradient(g):
-            return None, db.permute(0, 3, 1, 2), None, None
-        return None, (db * g.detach().float()).permute(0, 3, 1, 2), None, None
-
-
-def consistency_softmax_mse(a, b, weight=1.0, flags=None):
-    """consistency.py:30-35: ``weight * mse(softmax(flip(a)).detach(), softmax(b))`` of logical [N, C, H, W] logits"""
-    return _ConsistencyFn.apply(a, b, flags, float(weight))
+    return _PixelCriterionFn.apply(b, launch)
 
 
 # ------------------------------------------------------------------- mean teacher / entropy minimisation (csrc/semi_reg.hip)
@@ -2918,113 +2933,44 @@ def ema_update_(teacher_flat, student_flat, alpha, decay=0.0):
     return teacher_flat
 
 
-class _MTSoftmaxMSEFn(torch.autograd.Function):
-    """``weight * MSELoss(flip(T), softmax(student_logits))`` in one launch, ``T`` the teacher's output or its softmax; the
-    gradient w.r.t. the student's logits for a unit upstream gradient is written by the same launch (the teacher gets none)."""
-
-    @staticmethod
-    def forward(ctx, teacher, student, flags, weight, mode):
-        _n.require_gpu(teacher, student)
-        ts, ss = _class_map_storage(teacher.detach()), _class_map_storage(student.detach())
-        if ts.shape != ss.shape:
-            raise AssertionError(f"class maps {tuple(ts.shape)} / {tuple(ss.shape)} differ")
-        N, H, W, C = ss.shape
-        dev = ss.device
-        fl = _flip_flags_arg(flags, N, dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        ds = torch.empty_like(ss)
-        ws = torch.empty(_n.call("spcl_mt_softmax_mse_workspace_bytes", N, H, W), dtype=torch.uint8, device=dev)
-        _n.call("spcl_mt_softmax_mse", _n.ptr(ts), _n.ptr(ss), N, C, H, W, _n.ptr(fl), int(mode), c_float(weight),
-                _n.ptr(loss), _n.ptr(ds), _n.ptr(ws), ws.numel(), _n.stream())
-        ctx.save_for_backward(ds)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (ds,) = ctx.saved_tensors
-        if is_unit_gradient(g):
-            return None, ds.permute(0, 3, 1, 2), None, None, None
-        return None, (ds * g.detach().float()).permute(0, 3, 1, 2), None, None, None
-
-
 def mt_softmax_mse(teacher, student_logits, weight=1.0, flags=None, teacher_softmax=False):
     """mt.py:48-52: ``weight * mse(flip(teacher), softmax(student_logits))`` of logical [N, C, H, W] maps; with
     ``teacher_softmax`` the teacher's map is soft-maxed first (_mixins.py:147)"""
-    return _MTSoftmaxMSEFn.apply(teacher, student_logits, flags, float(weight), 1 if teacher_softmax else 0)
+    weight = float(weight)
 
+    def launch():
+        _n.require_gpu(teacher, student_logits)
+        ts, ss = _class_map_storage(teacher.detach()), _class_map_storage(student_logits.detach())
+        if ts.shape != ss.shape:
+            raise AssertionError(f"class maps {tuple(ts.shape)} / {tuple(ss.shape)} differ")
+        N, H, W, C = ss.shape
+        fl = _flip_flags_arg(flags, N, ss.device)
+        loss, ds, ws = _pixel_criterion_buffers(ss, "spcl_mt_softmax_mse_workspace_bytes")
+        _n.call("spcl_mt_softmax_mse", _n.ptr(ts), _n.ptr(ss), N, C, H, W, _n.ptr(fl), 1 if teacher_softmax else 0,
+                c_float(weight), _n.ptr(loss), _n.ptr(ds), _n.ptr(ws), ws.numel(), _n.stream())
+        return loss, ds
 
-class _EntropySoftmaxFn(torch.autograd.Function):
-    """``weight * Entropy(eps)(softmax(logits))`` in one launch; the gradient w.r.t. the logits for a unit upstream gradient
-    is written by the same launch."""
-
-    @staticmethod
-    def forward(ctx, logits, eps, weight):
-        _n.require_gpu(logits)
-        ls = _class_map_storage(logits.detach())
-        N, H, W, C = ls.shape
-        dev = ls.device
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dl = torch.empty_like(ls)
-        ws = torch.empty(_n.call("spcl_entropy_softmax_workspace_bytes", N, H, W), dtype=torch.uint8, device=dev)
-        _n.call("spcl_entropy_softmax", _n.ptr(ls), N, C, H, W, c_float(eps), c_float(weight), _n.ptr(loss), _n.ptr(dl),
-                _n.ptr(ws), ws.numel(), _n.stream())
-        ctx.save_for_backward(dl)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (dl,) = ctx.saved_tensors
-        if is_unit_gradient(g):
-            return dl.permute(0, 3, 1, 2), None, None
-        return (dl * g.detach().float()).permute(0, 3, 1, 2), None, None
+    return _PixelCriterionFn.apply(student_logits, launch)
 
 
 def entropy_softmax(logits, eps=1e-16, weight=1.0):
     """entmin.py:30-31: ``weight * mean over pixels of -sum_c p_c log(p_c + eps)``, ``p = softmax(logits)``, of logical
     [N, C, H, W] logits"""
-    return _EntropySoftmaxFn.apply(logits, float(eps), float(weight))
+    eps, weight = float(eps), float(weight)
+
+    def launch():
+        _n.require_gpu(logits)
+        ls = _class_map_storage(logits.detach())
+        N, H, W, C = ls.shape
+        loss, dl, ws = _pixel_criterion_buffers(ls, "spcl_entropy_softmax_workspace_bytes")
+        _n.call("spcl_entropy_softmax", _n.ptr(ls), N, C, H, W, c_float(eps), c_float(weight), _n.ptr(loss), _n.ptr(dl),
+                _n.ptr(ws), ws.numel(), _n.stream())
+        return loss, dl
+
+    return _PixelCriterionFn.apply(logits, launch)
 
 
 UCMT_MAX_NOISY = 16  # the K device pointers travel in the kernel's argument block
-
-
-class _UCMTSoftmaxMSEFn(torch.autograd.Function):
-    """The uncertainty-aware mean teacher's criterion in one launch (``spcl_ucmt_softmax_mse``): the loss, the gradient
-    w.r.t. the student's logits for a unit upstream gradient, the number of kept pixels and -- when ``out`` is a list -- the
-    mask.  The teacher and the noisy maps get no gradient."""
-
-    @staticmethod
-    def forward(ctx, teacher, noisy, student, flags, threshold, eps, weight, out):
-        _n.require_gpu(teacher, student, *noisy)
-        if not 1 <= len(noisy) <= UCMT_MAX_NOISY:
-            raise ValueError(f"ucmt_softmax_mse: {len(noisy)} noisy maps (1 <= K <= {UCMT_MAX_NOISY})")
-        ts, ss = _class_map_storage(teacher.detach()), _class_map_storage(student.detach())
-        ns = [_class_map_storage(t.detach()) for t in noisy]
-        for t in [ts] + ns:
-            if t.shape != ss.shape or t.device != ss.device:
-                raise AssertionError(f"class maps {tuple(t.shape)} on {t.device} / {tuple(ss.shape)} on {ss.device} differ")
-        N, H, W, C = ss.shape
-        dev = ss.device
-        fl = _flip_flags_arg(flags, N, dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        ds = torch.empty_like(ss)
-        kept = torch.empty((), dtype=torch.int64, device=dev)
-        mask = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if out is not None else None
-        ws = torch.empty(_n.call("spcl_ucmt_workspace_bytes", N, H, W), dtype=torch.uint8, device=dev)
-        _n.call("spcl_ucmt_softmax_mse", _n.ptr(ts), _n.ptr_array(ns), len(ns), _n.ptr(ss), N, C, H, W, _n.ptr(fl),
-                c_float(threshold), c_float(eps), c_float(weight), _n.ptr(loss), _n.ptr(ds), _n.ptr(kept), _n.ptr(mask),
-                _n.ptr(ws), ws.numel(), _n.stream())
-        if out is not None:
-            out.extend((kept, mask))
-        ctx.save_for_backward(ds)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (ds,) = ctx.saved_tensors
-        if is_unit_gradient(g):
-            return None, None, ds.permute(0, 3, 1, 2), None, None, None, None, None
-        return None, None, (ds * g.detach().float()).permute(0, 3, 1, 2), None, None, None, None, None
 
 
 def ucmt_softmax_mse(teacher, noisy_list, student_logits, threshold, weight=1.0, flags=None, eps=1e-16, out=None):
@@ -3034,8 +2980,32 @@ def ucmt_softmax_mse(teacher, noisy_list, student_logits, threshold, weight=1.0,
     average of the flipped maps is the flip of the average).  The gradient goes to the student only.  ``out`` (a list)
     receives ``(kept, mask)``: the number of pixels with mask = 1 as an int64 device scalar (no readback here) and the mask as
     uint8 [N, H, W] in the student's frame."""
-    return _UCMTSoftmaxMSEFn.apply(teacher, tuple(noisy_list), student_logits, flags, float(threshold), float(eps),
-                                   float(weight), out)
+    noisy = tuple(noisy_list)
+    threshold, eps, weight = float(threshold), float(eps), float(weight)
+
+    def launch():
+        _n.require_gpu(teacher, student_logits, *noisy)
+        if not 1 <= len(noisy) <= UCMT_MAX_NOISY:
+            raise ValueError(f"ucmt_softmax_mse: {len(noisy)} noisy maps (1 <= K <= {UCMT_MAX_NOISY})")
+        ts, ss = _class_map_storage(teacher.detach()), _class_map_storage(student_logits.detach())
+        ns = [_class_map_storage(t.detach()) for t in noisy]
+        for t in [ts] + ns:
+            if t.shape != ss.shape or t.device != ss.device:
+                raise AssertionError(f"class maps {tuple(t.shape)} on {t.device} / {tuple(ss.shape)} on {ss.device} differ")
+        N, H, W, C = ss.shape
+        dev = ss.device
+        fl = _flip_flags_arg(flags, N, dev)
+        loss, ds, ws = _pixel_criterion_buffers(ss, "spcl_ucmt_workspace_bytes")
+        kept = torch.empty((), dtype=torch.int64, device=dev)
+        mask = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if out is not None else None
+        _n.call("spcl_ucmt_softmax_mse", _n.ptr(ts), _n.ptr_array(ns), len(ns), _n.ptr(ss), N, C, H, W, _n.ptr(fl),
+                c_float(threshold), c_float(eps), c_float(weight), _n.ptr(loss), _n.ptr(ds), _n.ptr(kept), _n.ptr(mask),
+                _n.ptr(ws), ws.numel(), _n.stream())
+        if out is not None:
+            out.extend((kept, mask))
+        return loss, ds
+
+    return _PixelCriterionFn.apply(student_logits, launch)
 
 
 # ------------------------------------------------------------------------------------------------ mix-up (csrc/semi_reg.hip)
@@ -3110,41 +3080,26 @@ def _label_map_arg(t, B, H, W, name):
     return t.contiguous()
 
 
-class _MixupKLFn(torch.autograd.Function):
-    """``weight * KL_div(eps)(softmax(logits), lam * onehot(y) + (1 - lam) * onehot(y[index]))`` in one launch; the gradient
-    w.r.t. the logits for a unit upstream gradient is written by the same launch."""
-
-    @staticmethod
-    def forward(ctx, logits, target, target_tf, plan, eps, weight):
-        _n.require_gpu(logits, target, target_tf)
-        ls = _class_map_storage(logits.detach())
-        N2, H, W, C = ls.shape
-        dev = ls.device
-        index = _mixup_plan_arg(plan, N2, dev)
-        ya = _label_map_arg(target.detach(), N2 // 2, H, W, "target")
-        yb = _label_map_arg(target_tf.detach(), N2 // 2, H, W, "target_tf")
-        lam, oml = plan.pair
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dl = torch.empty_like(ls)
-        ws = torch.empty(_n.call("spcl_mixup_kl_workspace_bytes", N2, H, W), dtype=torch.uint8, device=dev)
-        _n.call("spcl_mixup_kl_onehot", _n.ptr(ls), _n.ptr(ya), _n.ptr(yb), _n.ptr(index), N2, C, H, W, c_float(lam),
-                c_float(oml), c_float(eps), c_float(weight), _n.ptr(loss), _n.ptr(dl), _n.ptr(ws), ws.numel(), _n.stream())
-        ctx.save_for_backward(dl)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (dl,) = ctx.saved_tensors
-        if is_unit_gradient(g):
-            return dl.permute(0, 3, 1, 2), None, None, None, None, None
-        return (dl * g.detach().float()).permute(0, 3, 1, 2), None, None, None, None, None
-
-
 def mixup_kl_onehot(logits, target, target_tf, plan, eps=1e-16, weight=1.0):
     """mixup.py:31,66-75: ``weight * KL_div(eps)(softmax(logits), mixed_y)`` of logical [2B, C, H, W] logits, ``mixed_y`` the
     plan's blend of the one-hot maps of ``cat([target, target_tf])`` and of their permutation (never built); targets
     [B, 1, H, W] or [B, H, W] integer label maps"""
-    return _MixupKLFn.apply(logits, target, target_tf, plan, float(eps), float(weight))
+    eps, weight = float(eps), float(weight)
+
+    def launch():
+        _n.require_gpu(logits, target, target_tf)
+        ls = _class_map_storage(logits.detach())
+        N2, H, W, C = ls.shape
+        index = _mixup_plan_arg(plan, N2, ls.device)
+        ya = _label_map_arg(target.detach(), N2 // 2, H, W, "target")
+        yb = _label_map_arg(target_tf.detach(), N2 // 2, H, W, "target_tf")
+        lam, oml = plan.pair
+        loss, dl, ws = _pixel_criterion_buffers(ls, "spcl_mixup_kl_workspace_bytes")
+        _n.call("spcl_mixup_kl_onehot", _n.ptr(ls), _n.ptr(ya), _n.ptr(yb), _n.ptr(index), N2, C, H, W, c_float(lam),
+                c_float(oml), c_float(eps), c_float(weight), _n.ptr(loss), _n.ptr(dl), _n.ptr(ws), ws.numel(), _n.stream())
+        return loss, dl
+
+    return _PixelCriterionFn.apply(logits, launch)
 
 
 # --------------------------------------------------------------------------------------------- DCGAN discriminator

@@ -149,3 +149,24 @@ def test_entropy_softmax_vs_float64(shape):
     # the float path of the restated criterion on the device agrees as well
     dev = weight * Entropy()(_cl(x).softmax(1))
     assert abs(float(dev) - float(ref)) <= 1e-5 * float(ref)
+
+
+@pytest.mark.parametrize("shape,flags", [((3, 4, 20, 24), [3, 0, 1]),   # 1440 pixels: six workgroups, the last partly empty
+                                         ((3, 4, 20, 24), None),
+                                         ((2, 2, 5, 7), [2, 1]),         # below one workgroup, C = 2
+                                         ((1, 16, 9, 33), [3]),          # the maximum C
+                                         # 288 workgroups: the closing sum fetches a second, partial batch of 32 partials
+                                         ((2, 4, 192, 192), [1, 2])])
+def test_consistency_is_the_soft_teacher_criterion_bit_for_bit(shape, flags):
+    """``consistency_softmax_mse`` and ``mt_softmax_mse(teacher_softmax=True)`` are one launch of one kernel: the same bits"""
+    from spcl_amd import functional as F_hip
+    g = torch.Generator().manual_seed(12)
+    a, b = torch.randn(*shape, generator=g), torch.randn(*shape, generator=g)
+    fl = None if flags is None else torch.tensor(flags, dtype=torch.uint8, device=DEV)
+    runs = []
+    for criterion in (F_hip.consistency_softmax_mse, lambda *args: F_hip.mt_softmax_mse(*args, teacher_softmax=True)):
+        bd = _cl(b).requires_grad_(True)
+        loss = criterion(_cl(a), bd, 2.5, fl)
+        (3.0 * loss).backward()
+        runs.append((loss.detach().clone(), bd.grad.clone()))
+    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
