@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 20
+#define SPCL_ABI_VERSION 21
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -1120,6 +1120,46 @@ int spcl_discr_head_forward(const float* x, int N, int H, int W, int C, const fl
                             int y, float* t, float* d, float* loss, float* dt, void* ws, size_t ws_bytes, void* stream);
 int spcl_discr_head_backward(const float* x, int N, int H, int W, int C, const float* scale, const float* shift, const float* w,
                              const float* dt, const float* grad, float* du, float* dw, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- MINE baseline: the statistics network's two ends (csrc/mine.hip) ---
+ * The statistics network of semi_seg/mi_estimator/mineestimator.py:19-30 is two conv3x3 + BatchNorm + ReLU layers (the kernels
+ * above) between an input that is a concatenation and a tail that is a pooled linear logit; these four entry points are those
+ * two ends (ABI 21).  dtype: SPCL_F32 / SPCL_BF16, the storage type of every map; CS(c) = c rounded up to 16.  Every sum has a
+ * fixed order (no floating-point atomics): bitwise reproducible.
+ *
+ *   spcl_mine_pairs_forward: replaces torch.cat([feat2[1:], feat2[0:1]]), the two torch.cat([feat1, .], dim=1) of
+ *                    mineestimator.py:33-35 and the per-sample flips of semi_seg/epochers/_mixins.py:79-82.  feat [2n][H][W][CS(C)]
+ *                    is the extracted feature (rows 0..n-1: the unlabelled images, rows n..2n-1: their transformed copies), flags
+ *                    uint8 [n] the batch's flips (bit 0 flips H, bit 1 flips W; NULL: none).  joint, marg [n][H][W][CS(2C)]:
+ *                    channels 0..C-1 of both are feat[n + i]; channels C..2C-1 are flip_i(feat[i]) in joint and
+ *                    flip_j(feat[j]), j = (i + 1) mod n, in marg; pad channels are 0.  One launch; 16-byte accesses when
+ *                    C % 16 == 0 and the three pointers are 16-byte aligned, element-wise ones otherwise.
+ *   spcl_mine_pairs_backward: its gradient as one gather: dfeat[n + i] = dJ[i][:C] + dM[i][:C], dfeat[i] = flip_i(dJ[i][C:] +
+ *                    dM[(i - 1) mod n][C:]), added in f32 and rounded once; pad channels of dfeat [2n][H][W][CS(C)] are 0.
+ *   spcl_mine_head_forward: replaces nn.AdaptiveMaxPool2d((1, 1)) / Flatten / nn.Linear(C / 2, 1) of mineestimator.py:27-29 and
+ *                    the two F.softplus(.).mean() of :34-35, for both passes in one launch.  act_joint, act_marg
+ *                    [n][H][W][CS(C / 2)] are the second layer's stored activations (C the network's input_dim: even,
+ *                    C / 2 <= 256).  maxima [2][n][C / 2] (f32) and argmax [2][n][C / 2] (int32, h W + w; the first index in
+ *                    row-major order among equal values, a NaN wins) -- pass 0 is the joint one; t [2][n] = b[0] + sum_c w[c]
+ *                    maxima[c], an f32 FMA chain in channel order; loss[0] = mean_i sp(t[1][i]) + mean_i sp(t[0][i]) = Em - Ej of
+ *                    :34-36, sp(t) = max(t, 0) + log1p(exp(-|t|)), each mean added in index order in double.  A workgroup takes
+ *                    256 pixels of one (pass, sample), lanes along the channel axis; the workgroup that finishes last folds the
+ *                    slabs in index order and forms logits and loss.  ws: spcl_mine_head_workspace_bytes(n, H, W, C) (0: a
+ *                    shape the entry refuses).
+ *   spcl_mine_head_backward: one launch.  dt = sigmoid(t) * (grad ? grad[0] : 1) / n (grad a device scalar); dw [C / 2] = sum dt
+ *                    maxima and db [1] = sum dt over (pass, sample) in index order (either may be NULL); dact_joint, dact_marg
+ *                    [n][H][W][CS(C / 2)] are written densely: w[c] dt at the argmax, 0 everywhere else.  argmax is only ever
+ *                    compared with a pixel index, never used as an address. */
+int spcl_mine_pairs_forward(const void* feat, const uint8_t* flags, int dtype, int n, int H, int W, int C, void* joint, void* marg,
+                            void* stream);
+int spcl_mine_pairs_backward(const void* djoint, const void* dmarg, const uint8_t* flags, int dtype, int n, int H, int W, int C,
+                             void* dfeat, void* stream);
+size_t spcl_mine_head_workspace_bytes(int n, int H, int W, int C);
+int spcl_mine_head_forward(const void* act_joint, const void* act_marg, int dtype, int n, int H, int W, int C, const float* w,
+                           const float* b, float* t, float* maxima, int* argmax, float* loss, void* ws, size_t ws_bytes,
+                           void* stream);
+int spcl_mine_head_backward(const float* t, const float* maxima, const int* argmax, const float* w, const float* grad, int dtype,
+                            int n, int H, int W, int C, void* dact_joint, void* dact_marg, float* dw, float* db, void* stream);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,9 @@ _MIRRORED = {
     "semi_seg.hooks.mixup": "semi_seg.hooks.mixup",
     "semi_seg.hooks.ucmt": "semi_seg.hooks.ucmt",
     "semi_seg.hooks.midl": "semi_seg.hooks.midl",
+    "semi_seg.hooks.mine": "semi_seg.hooks.mine",
+    "semi_seg.mi_estimator": "semi_seg.mi_estimator",
+    "semi_seg.mi_estimator.mineestimator": "semi_seg.mi_estimator.mine",
     "semi_seg.epochers": "semi_seg.epochers",
     "semi_seg.epochers.new_pretrain": "semi_seg.epochers.pretrain",
     "semi_seg.epochers.new_epocher": "semi_seg.epochers.finetune",

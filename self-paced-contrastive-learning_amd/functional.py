@@ -3380,3 +3380,164 @@ def discr_bn_conv(x, gamma, beta, weight, bn: RowsBN, *, weight_grads=True):
 
 def discr_bn_head(x, gamma, beta, weight, bn: RowsBN, *, label=None, weight_grads=True):
     return _DiscrBnHeadFn.apply(x, gamma, beta, weight, bn, label, bool(weight_grads))
+
+
+# --------------------------------------------------------------------------------------------- MINE statistics network
+class _MinePairsFn(torch.autograd.Function):
+    """The statistics network's two inputs from the extracted feature ``feat`` [2n, C, H, W] (rows 0..n-1: the unlabelled
+    images, rows n..2n-1: their transformed copies): ``cat(feat1, feat2)`` and ``cat(feat1, roll(feat2))`` of
+    mineestimator.py:33-35 with ``feat2 = flip(feat[:n])`` of _mixins.py:79-82, one launch each way (spcl_mine_pairs_*)."""
+
+    @staticmethod
+    def forward(ctx, feat, flags, dtype):
+        _n.require_gpu(feat)
+        if feat.dim() != 4 or feat.shape[0] < 2 or feat.shape[0] % 2:
+            raise ValueError(f"mine_pairs: a feature of 2n samples [2n, C, H, W], got {tuple(feat.shape)}")
+        N2, C, H, W = feat.shape
+        n = N2 // 2
+        flags = _flip_flags_arg(flags, n, feat.device)
+        xs = to_nhwc_padded(feat.detach(), dtype)
+        c2s = _ru16(2 * C)
+        joint = torch.empty(n, H, W, c2s, dtype=dtype, device=feat.device)
+        marg = torch.empty(n, H, W, c2s, dtype=dtype, device=feat.device)
+        _n.call("spcl_mine_pairs_forward", _n.ptr(xs), _n.ptr(flags), _n.dtype_code(dtype), n, H, W, C, _n.ptr(joint),
+                _n.ptr(marg), _n.stream())
+        ctx.flags = flags
+        ctx.meta = (n, C, H, W, xs.shape[3], dtype, feat.dtype)
+        return nhwc_to_logical(joint, 2 * C), nhwc_to_logical(marg, 2 * C)
+
+    @staticmethod
+    def backward(ctx, dj, dm):
+        n, C, H, W, cs, dtype, xdt = ctx.meta
+        djs, dms = to_nhwc_padded(dj, dtype), to_nhwc_padded(dm, dtype)
+        dfeat = torch.empty(2 * n, H, W, cs, dtype=dtype, device=dj.device)
+        _n.call("spcl_mine_pairs_backward", _n.ptr(djs), _n.ptr(dms), _n.ptr(ctx.flags), _n.dtype_code(dtype), n, H, W, C,
+                _n.ptr(dfeat), _n.stream())
+        g = nhwc_to_logical(dfeat, C)
+        return (g if g.dtype == xdt else g.to(xdt)), None, None
+
+
+def _mine_dtype(dtype):
+    if dtype is None:
+        from . import config as _config
+        dtype = _config.get_compute_dtype()
+    return dtype
+
+
+def mine_pairs(feat, flags=None, dtype=None):
+    """-> (joint, marg), logical [n, 2C, H, W] views over NHWC storage of the compute dtype; ``flags``: uint8 [n] or None"""
+    return _MinePairsFn.apply(feat, flags, _mine_dtype(dtype))
+
+
+class _MineHeadFn(torch.autograd.Function):
+    """``AdaptiveMaxPool2d((1, 1)) -> Flatten -> Linear(C / 2, 1)`` of the two passes' stored activations and
+    ``softplus(t_marg).mean() + softplus(t_joint).mean()`` (mineestimator.py:27-29,34-36) in one launch; the backward, one
+    launch too, writes the two dense activation gradients the BatchNorm-ReLU backward of ``conv_bn_relu`` consumes.
+    ``dead``: parameters that cannot move the loss (the convolution biases in front of a training-mode BatchNorm): their
+    gradient is exact zeros rather than None."""
+
+    @staticmethod
+    def forward(ctx, act_j, act_m, lw, lb, dtype, out, *dead):
+        _n.require_gpu(act_j, act_m, lw, lb)
+        if act_j.dim() != 4 or act_j.shape != act_m.shape:
+            raise ValueError(f"mine_head: two activations of one shape [n, C/2, H, W], got {tuple(act_j.shape)} and "
+                             f"{tuple(act_m.shape)}")
+        n, CH, H, W = act_j.shape
+        if lw.numel() != CH or lb.numel() != 1:
+            raise ValueError(f"mine_head: Linear({CH}, 1), got a weight {tuple(lw.shape)} and a bias {tuple(lb.shape)}")
+        dev = act_j.device
+        aj, am = to_nhwc_padded(act_j.detach(), dtype), to_nhwc_padded(act_m.detach(), dtype)
+        w = lw.detach().reshape(-1).contiguous().float()
+        b = lb.detach().reshape(1).contiguous().float()
+        t = torch.empty(2, n, dtype=torch.float32, device=dev)
+        mx = torch.empty(2, n, CH, dtype=torch.float32, device=dev)
+        arg = torch.empty(2, n, CH, dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        nbytes = _n.call("spcl_mine_head_workspace_bytes", n, H, W, 2 * CH)
+        if nbytes == 0:
+            raise ValueError(f"mine_head: at most 256 pooled channels and a map below 2^24 pixels (got {CH}, {H} x {W})")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _n.call("spcl_mine_head_forward", _n.ptr(aj), _n.ptr(am), _n.dtype_code(dtype), n, H, W, 2 * CH, _n.ptr(w), _n.ptr(b),
+                _n.ptr(t), _n.ptr(mx), _n.ptr(arg), _n.ptr(loss), _n.ptr(ws), nbytes, _n.stream())
+        if out is not None:
+            out.update(t=t, maxima=mx, argmax=arg)
+        ctx.save_for_backward(t, mx, arg, w)
+        ctx.params = (lw, lb)
+        ctx.dead = tuple((tuple(d.shape), d.numel()) for d in dead)
+        ctx.meta = (n, CH, H, W, aj.shape[3], dtype, act_j.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        t, mx, arg, w = ctx.saved_tensors
+        n, CH, H, W, cs, dtype, adt = ctx.meta
+        lw, lb = ctx.params
+        dev = t.device
+        ng = ctx.needs_input_grad
+        grad = None if is_unit_gradient(g) else g.detach().float().reshape(1).contiguous()
+        dj = torch.empty(n, H, W, cs, dtype=dtype, device=dev)
+        dm = torch.empty(n, H, W, cs, dtype=dtype, device=dev)
+        dw = _grad_buffer(take_grad_sink(lw, ng[2]), (CH,), dev) if ng[2] else None
+        db = _grad_buffer(take_grad_sink(lb, ng[3]), (1,), dev) if ng[3] else None
+        _n.call("spcl_mine_head_backward", _n.ptr(t), _n.ptr(mx), _n.ptr(arg), _n.ptr(w), _n.ptr(grad), _n.dtype_code(dtype), n,
+                H, W, 2 * CH, _n.ptr(dj), _n.ptr(dm), _n.ptr(dw), _n.ptr(db), _n.stream())
+        gj, gm = nhwc_to_logical(dj, CH), nhwc_to_logical(dm, CH)
+        if adt != dtype:
+            gj, gm = gj.to(adt), gm.to(adt)
+        zeros, at = [], 0
+        if ctx.dead:
+            flat = torch.zeros(sum(k for _, k in ctx.dead), dtype=torch.float32, device=dev)
+            for i, (shape, k) in enumerate(ctx.dead):
+                zeros.append(flat[at:at + k].view(shape) if ng[6 + i] else None)
+                at += k
+        return (gj if ng[0] else None, gm if ng[1] else None, None if dw is None else dw.view(lw.shape),
+                None if db is None else db.view(lb.shape), None, None, *zeros)
+
+
+def mine_head(act_joint, act_marg, weight, bias, dtype=None, dead=(), out=None):
+    """-> ``Em - Ej`` (0-dim f32).  ``out``: a dict that receives the logits ``t`` [2, n], the pooled ``maxima`` [2, n, C/2] and
+    their ``argmax`` [2, n, C/2] (pass 0 is the joint one)"""
+    return _MineHeadFn.apply(act_joint, act_marg, weight, bias, _mine_dtype(dtype), out, *dead)
+
+
+class MineBN:
+    """one ``nn.BatchNorm2d`` of the statistics network as the kernels see it"""
+    __slots__ = ("running_mean", "running_var", "num_batches_tracked", "training", "track", "momentum", "eps")
+
+    def __init__(self, running_mean, running_var, num_batches_tracked, training, track, momentum, eps):
+        self.running_mean, self.running_var, self.num_batches_tracked = running_mean, running_var, num_batches_tracked
+        self.training, self.track, self.momentum, self.eps = bool(training), bool(track), float(momentum), float(eps)
+
+
+def _mine_layer(x, w, b, gamma, beta, bn: MineBN, dtype):
+    """``Conv2d(., ., 3, 1, 1)`` WITH bias -> BatchNorm2d -> ReLU.  With batch statistics the bias cancels in the
+    normalisation, so the kernels never see it; only the running mean does (``+= momentum * bias``, what tracking the biased
+    output would have added).  With running statistics the bias moves into the BatchNorm shift: normalising ``conv + b`` with
+    mean ``m`` is normalising ``conv`` with mean ``m - b``."""
+    rm, rv, nbt = bn.running_mean, bn.running_var, bn.num_batches_tracked
+    if not bn.training:
+        rm = rm.float() - b.detach().float()
+    cfg = BlockCfg(dtype, bn.training, bn.momentum, bn.eps, (bn.track,), True, False, False, ((rm, rv, nbt),))
+    act = conv_bn_relu(x, w, gamma, beta, cfg)
+    if bn.training and bn.track:
+        with torch.no_grad():
+            bn.running_mean.add_(b.detach().to(bn.running_mean.dtype), alpha=bn.momentum)
+    return act
+
+
+def mine_loss(feat, flags, layers, linear, dtype=None, out=None):
+    """``MineEstimator.forward`` (mineestimator.py:32-36) on the extracted feature ``feat`` [2n, C, H, W] and the batch's flip
+    flags: ``Em - Ej``.  ``layers``: two tuples ``(conv weight, conv bias, bn weight, bn bias, MineBN)``; ``linear``:
+    ``(weight [1, C/2], bias [1])``.  The joint pass runs first, each pass with its own batch statistics."""
+    dtype = _mine_dtype(dtype)
+    joint, marg = mine_pairs(feat, flags, dtype)
+    dtc, (H, W) = _n.dtype_code(dtype), feat.shape[2:]
+    packed = [_pack_both(layer[0], dtc, dtype) for layer in layers]  # once: both passes use the same weights
+    acts = []
+    for x in (joint, marg):
+        for (w, b, gamma, beta, bn), pk in zip(layers, packed):
+            _PREPACKED[(w.data_ptr(), w._version, dtc, int(H), int(W))] = pk  # (consumed by the call below: take_prepacked)
+            x = _mine_layer(x, w, b, gamma, beta, bn, dtype)
+        acts.append(x)
+    dead = tuple(b for _, b, _, _, bn in layers if bn.training and b.requires_grad)
+    return mine_head(acts[0], acts[1], linear[0], linear[1], dtype, dead=dead, out=out)

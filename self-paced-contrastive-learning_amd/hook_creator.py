@@ -15,7 +15,11 @@ lets one config hold either baseline.  Refused during pre-training like the othe
 ``MIDLPaperParameters`` builds the MIDL baseline (``create_midl_hook``: the consistency hook plus the patch-wise IIC
 segmentation criterion): the keys of config/specific/midl.yaml (``iic_weight``, ``padding``, ``patch_size``) plus
 ``consistency_weight`` and ``name``, which the reference's old-API ``MIDLTrainer`` reads from ``UDARegCriterion``
-(semi_seg/trainers/trainer.py:24-26,42) -- a section of its own for the same reason.  Refused during pre-training too."""
+(semi_seg/trainers/trainer.py:24-26,42) -- a section of its own for the same reason.  Refused during pre-training too.
+``MineParameters`` builds the MINE baseline (``create_mine_hooks``: one statistics network per feature): ``feature_names``
+and ``weights``, where the reference's old-API ``MineTrainer`` (trainer.py:98-107) reads ``IICRegParameters.weight`` and
+``FeatureExtractor.feature_names`` / ``feature_importance`` -- ``weights[i] = weight * imp_i / sum(imp)``.  Refused during
+pre-training as well."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -30,6 +34,7 @@ _SEMI_SECTIONS = (
     ("EntropyMinParameters", "create_entropy_min_hook", False, False),
     ("UCMeanTeacherParameters", "create_uc_mean_teacher_hook", True, True),
     ("MIDLPaperParameters", "create_midl_hook", False, False),
+    ("MineParameters", "create_mine_hooks", True, False),
 )
 
 

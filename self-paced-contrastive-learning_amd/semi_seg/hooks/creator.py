@@ -6,7 +6,8 @@ contrast_on) triple combined into one TrainerHook -- and the UDA-IIC factories `
 (semi_seg/trainers/trainer.py:227-271, from ``EntropyMinParameters`` / ``MeanTeacherParameters``); the hook names are its
 trainer-registry keys (semi_seg/trainers/__init__.py:11-12).  ``create_uc_mean_teacher_hook`` likewise stands for
 ``UCMeanTeacherTrainer`` (trainer.py:274-290, registry key ``ucmeanteacher``) and ``create_midl_hook`` for ``MIDLTrainer``
-(trainer.py:39-60, registry key ``midl``)."""
+(trainer.py:39-60, registry key ``midl``) and ``create_mine_hooks`` for ``MineTrainer`` (trainer.py:98-107, registry key
+``mine``)."""
 from typing import List, Union
 
 from ...contrastyou.hooks.base import CombineTrainerHook
@@ -16,6 +17,7 @@ from .discretemi import DiscreteMITrainHook
 from .entmin import EntropyMinTrainerHook
 from .infonce import INFONCEHook, SelfPacedINFONCEHook, decoder_names
 from .midl import MIDLPaperTrainerHook
+from .mine import MineTrainHook
 from .mt import MeanTeacherTrainerHook
 from .ucmt import UCMeanTeacherTrainerHook
 
@@ -137,3 +139,14 @@ def create_midl_hook(*, consistency_weight: float, iic_weight: float = 0.1, padd
         raise NotImplementedError(f"MIDL consistency criterion {name!r}: only 'mse' is mirrored")
     return CombineTrainerHook(ConsistencyTrainerHook(name="consistency", weight=consistency_weight),
                               MIDLPaperTrainerHook(name="midl", weight=iic_weight, padding=padding, patch_size=patch_size))
+
+
+def create_mine_hooks(*, model, feature_names: Union[str, List[str]], weights: Union[float, List[float]]):
+    """``MineParameters``: one MINE hook ``mine/<feature>`` per feature, each with a statistics network of its own
+    (mineestimator.py:39-50).  The reference multiplies the ``feature_importance``-weighted average of the per-feature losses
+    by ``IICRegParameters.weight`` (_mixins.py:93, trainer.py:98-107): ``weights[i] = weight * imp_i / sum(imp)`` is that sum."""
+    feature_names = _listify(feature_names, 1)
+    weights = ntuple(len(feature_names))(weights)
+    hooks = [MineTrainHook(name=f"mine/{f.lower()}", model=model, feature_name=f, weight=w)
+             for f, w in zip(feature_names, weights)]
+    return CombineTrainerHook(*hooks)
