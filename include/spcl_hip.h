@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 21
+#define SPCL_ABI_VERSION 22
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -1160,6 +1160,32 @@ int spcl_mine_head_forward(const void* act_joint, const void* act_marg, int dtyp
                            void* stream);
 int spcl_mine_head_backward(const float* t, const float* maxima, const int* argmax, const float* w, const float* grad, int dtype,
                             int n, int H, int W, int C, void* dact_joint, void* dact_marg, float* dw, float* db, void* stream);
+
+/* ---------------------------------------------------------------- PICA baseline: partition-uncertainty-index criteria (csrc/pica.hip) ---
+ * contrastyou/losses/pica_loss.py of the reference on the cluster heads of the IIC criteria (ABI 22).  Float64 from the
+ * probabilities / the joint on, every sum in a fixed order: bitwise reproducible.  ws: spcl_pica_workspace_bytes(S).
+ *
+ *   spcl_pica_seg_loss: replaces pica_loss.py:63-73,81-84 (PUISegLoss from the F.conv2d joint on: min-shift, per-displacement
+ *                    normalisation, symmetrisation, mean over the T^2 displacements, -mean(I log(P + 1e-16))) and its autograd.
+ *                    The joint comes as spcl_iic_joint_forward's 32.32 fixed-point jacc or as an f32 jf32 [S][T][T][K][K]
+ *                    (exactly one); 2 <= K <= 32, T odd <= 15.  One workgroup per subhead.  With ce_s the criterion of subhead s:
+ *                    loss[0] = scale * sum_s (ce_s + lamda_ne), ce_out[0] (nullable) = scale * sum_s ce_s, dj = d loss / d J in
+ *                    the layout spcl_iic_joint_backward reads (the min is detached), j_out (nullable, with jacc) = J in f32.
+ *                    lamda_ne: lamda times the balance term of pica_loss.py:76-77, which is a constant of the shape there (the
+ *                    mean runs over the class axis of the permuted map): lamda * (log M - (M / K) log K), M = N H W.
+ *   spcl_pica_global_loss: replaces PUILoss.forward (pica_loss.py:31-38) and its autograd.  lx / ly: logits rows [N][ld] f32,
+ *                    subhead s in columns s*K .. s*K+K-1, the grouped softmax applied as the rows are read; any N >= 1.  One
+ *                    launch, one workgroup per subhead, two passes over the rows.  loss[0] = scale * sum_s (ce_s + lamda ne_s)
+ *                    (ce_s the cross-entropy of the cosine matrix of the columns against its diagonal, ne_s = log K + sum_k
+ *                    p_k log p_k of the column means of x, no epsilon), ce_out[0] (nullable) = scale * sum_s ce_s, dlx / dly =
+ *                    d loss / d lx, d loss / d ly (times *gscale when non-NULL); the columns s*K + k are written, the others
+ *                    are left alone. */
+size_t spcl_pica_workspace_bytes(int S);
+int spcl_pica_seg_loss(const long long* jacc, const float* jf32, int S, int K, int T, double lamda_ne, float scale, float* j_out,
+                       float* loss, float* ce_out, float* dj, void* ws, size_t ws_bytes, void* stream);
+int spcl_pica_global_loss(const float* lx, const float* ly, long ld, int N, int S, int K, float lamda, float scale,
+                          const float* gscale, float* loss, float* ce_out, float* dlx, float* dly, void* ws, size_t ws_bytes,
+                          void* stream);
 
 #ifdef __cplusplus
 }

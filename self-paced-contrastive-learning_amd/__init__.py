@@ -20,6 +20,8 @@ _MIRRORED = {
     "contrastyou.losses.contrast_loss": "contrastyou.losses.contrast_loss",
     "contrastyou.losses.contrast_loss3": "contrastyou.losses.contrast_loss3",
     "contrastyou.losses.iic_loss": "contrastyou.losses.iic_loss",
+    "contrastyou.losses.pica_loss": "contrastyou.losses.pica_loss",
+    "contrastyou.losses.wrappers": "contrastyou.losses.wrappers",
     "contrastyou.meters": "contrastyou.meters",
     "contrastyou.projectors": "contrastyou.projectors",
     "contrastyou.projectors.heads": "contrastyou.projectors.heads",
@@ -43,6 +45,8 @@ _MIRRORED = {
     "semi_seg.hooks.ucmt": "semi_seg.hooks.ucmt",
     "semi_seg.hooks.midl": "semi_seg.hooks.midl",
     "semi_seg.hooks.mine": "semi_seg.hooks.mine",
+    "semi_seg.hooks.pica": "semi_seg.hooks.pica",
+    "semi_seg.utils": "semi_seg.utils",
     "semi_seg.mi_estimator": "semi_seg.mi_estimator",
     "semi_seg.mi_estimator.mineestimator": "semi_seg.mi_estimator.mine",
     "semi_seg.epochers": "semi_seg.epochers",

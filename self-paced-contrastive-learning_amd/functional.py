@@ -3,6 +3,7 @@ no host synchronisation anywhere in this file."""
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from ctypes import c_double, c_float, c_int
 
@@ -2802,6 +2803,100 @@ def iic_loss_from_joint(j, *, dense=True, scale=1.0):
     _n.call("spcl_iic_loss", None, _n.ptr(jc), S, K, T, int(dense), c_float(scale), None, _n.ptr(loss), _n.ptr(dj),
             _n.ptr(flag), _n.ptr(ws), ws.numel(), _n.stream())
     return loss, dj, flag
+
+
+def pica_balance_constant(M: int, K: int) -> float:
+    """the balance term of PUISegLoss (pica_loss.py:76-77) on the simplex: its ``mean(0)`` runs over the class axis of the
+    permuted [K, N, H, W] map, so ``p`` holds ``M = N H W`` entries that all equal 1/K -> ``log M - (M / K) log K``"""
+    return math.log(M) - (M / K) * math.log(K)
+
+
+def _pica_global_launch(xs, ys, S, K, lamda, scale, gs):
+    """-> (loss, ce, dlx, dly) of [N, 1, 1, S*K] logits rows (spcl_pica_global_loss; ``gs``: a device scalar or None)"""
+    N, ld, dev = xs.shape[0], xs.shape[3], xs.device
+    loss, ce = torch.empty((), dtype=torch.float32, device=dev), torch.empty((), dtype=torch.float32, device=dev)
+    dlx, dly = torch.empty_like(xs), torch.empty_like(ys)
+    ws = torch.empty(_n.call("spcl_pica_workspace_bytes", S), dtype=torch.uint8, device=dev)
+    _n.call("spcl_pica_global_loss", _n.ptr(xs), _n.ptr(ys), ld, N, S, K, c_float(lamda), c_float(scale), _n.ptr(gs),
+            _n.ptr(loss), _n.ptr(ce), _n.ptr(dlx), _n.ptr(dly), _n.ptr(ws), ws.numel(), _n.stream())
+    return loss, ce, dlx, dly
+
+
+class _PICALossFn(torch.autograd.Function):
+    """The PICA criteria of S subheads on two logit maps, logical [N, S*K, H, W] f32 (channels-last storage).  Dense
+    (PUISegLoss): ``_IICLossFn``'s three launches with spcl_pica_seg_loss as the middle one (X read through its per-sample
+    flips).  Global (PUILoss; H = W = 1, no flips): one launch that leaves the loss and both gradients.
+    Returns the loss; ``out`` receives (ce, J f32 [S,T,T,K,K] or None)."""
+
+    @staticmethod
+    def forward(ctx, lx, ly, flags, S, K, pad, dense, lamda, scale, out):
+        _n.require_gpu(lx, ly)
+        xs, ys = _class_map_storage(lx.detach()), _class_map_storage(ly.detach())
+        if xs.shape != ys.shape or xs.shape[3] != S * K:
+            raise AssertionError(f"logit maps {tuple(xs.shape)} / {tuple(ys.shape)} do not hold {S} x {K} clusters")
+        N, H, W, ld = xs.shape
+        dev = xs.device
+        ctx.dense, ctx.meta = dense, (S, K, pad, lamda, scale)
+        if not dense:
+            if H != 1 or W != 1 or flags is not None or pad != 0:
+                raise ValueError("pica_loss(dense=False): [N, S*K, 1, 1] logits, no flags, no padding")
+            loss, ce, dlx, dly = _pica_global_launch(xs, ys, S, K, lamda, scale, None)
+            out.extend([ce, None])
+            ctx.save_for_backward(xs, ys, dlx, dly)
+            return loss
+        T = 2 * pad + 1
+        fl = _flip_flags_arg(flags, N, dev)
+        jacc = torch.empty(_n.call("spcl_iic_joint_workspace_bytes", S, K, pad) // 8, dtype=torch.int64, device=dev)
+        _n.call("spcl_iic_joint_forward", _n.ptr(xs), _n.ptr(ys), ld, N, H, W, S, K, pad, _n.ptr(fl), _n.ptr(jacc), _n.stream())
+        jf = torch.empty(S, T, T, K, K, dtype=torch.float32, device=dev)
+        dj = torch.empty_like(jf)
+        loss, ce = torch.empty((), dtype=torch.float32, device=dev), torch.empty((), dtype=torch.float32, device=dev)
+        ws = torch.empty(_n.call("spcl_pica_workspace_bytes", S), dtype=torch.uint8, device=dev)
+        _n.call("spcl_pica_seg_loss", _n.ptr(jacc), None, S, K, T, c_double(lamda * pica_balance_constant(N * H * W, K)),
+                c_float(scale), _n.ptr(jf), _n.ptr(loss), _n.ptr(ce), _n.ptr(dj), _n.ptr(ws), ws.numel(), _n.stream())
+        out.extend([ce, jf])
+        ctx.save_for_backward(xs, ys, dj, fl)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        S, K, pad, lamda, scale = ctx.meta
+        gs = None if is_unit_gradient(g) else g.detach().float().reshape(1).contiguous()
+        if ctx.dense:
+            xs, ys, dj, fl = ctx.saved_tensors
+            N, H, W, ld = xs.shape
+            dlx, dly = torch.empty_like(xs), torch.empty_like(ys)
+            _n.call("spcl_iic_joint_backward", _n.ptr(xs), _n.ptr(ys), ld, N, H, W, S, K, pad, _n.ptr(fl), _n.ptr(dj),
+                    _n.ptr(gs), _n.ptr(dlx), _n.ptr(dly), _n.stream())
+        else:
+            xs, ys, dlx, dly = ctx.saved_tensors
+            if gs is not None:  # (the saved gradients are for a unit upstream gradient: run the launch again with the scalar)
+                _, _, dlx, dly = _pica_global_launch(xs, ys, S, K, lamda, scale, gs)
+        return dlx.permute(0, 3, 1, 2), dly.permute(0, 3, 1, 2), None, None, None, None, None, None, None, None
+
+
+def pica_loss(lx, ly, *, num_subheads, num_clusters, padding=0, dense=True, lamda=2.0, scale=1.0, flags=None, out=None):
+    """``scale * sum_s criterion(softmax(flip(lx)_s), softmax(ly_s))`` (PUISegLoss(lamda, padding) when ``dense``, PUILoss(lamda)
+    otherwise: pica_loss.py) of logical [N, S*K, H, W] logits; differentiable w.r.t. both maps.  The dense criterion's balance
+    term is the constant ``pica_balance_constant`` (no gradient).  ``out`` (a list) receives (ce, J): ``ce`` the
+    cross-entropy part of the returned loss, ``J`` the dense joint (None for the global criterion)."""
+    return _PICALossFn.apply(lx, ly, flags, int(num_subheads), int(num_clusters), int(padding), bool(dense), float(lamda),
+                             float(scale), [] if out is None else out)
+
+
+def pica_seg_loss_from_joint(j, *, lamda=2.0, ne=0.0, scale=1.0):
+    """-> (loss, ce, dJ) of an f32 joint [S, T, T, K, K] with the balance term ``ne`` given (spcl_pica_seg_loss on a given J; a
+    check tool for the criterion)"""
+    _n.require_gpu(j)
+    jc = j.detach().float().contiguous()
+    S, T, _, K, _ = jc.shape
+    loss = torch.empty((), dtype=torch.float32, device=jc.device)
+    ce = torch.empty((), dtype=torch.float32, device=jc.device)
+    dj = torch.empty_like(jc)
+    ws = torch.empty(_n.call("spcl_pica_workspace_bytes", S), dtype=torch.uint8, device=jc.device)
+    _n.call("spcl_pica_seg_loss", None, _n.ptr(jc), S, K, T, c_double(float(lamda) * float(ne)), c_float(scale), None,
+            _n.ptr(loss), _n.ptr(ce), _n.ptr(dj), _n.ptr(ws), ws.numel(), _n.stream())
+    return loss, ce, dj
 
 
 def iic_patch_starts(h: int, patch_size: int):

@@ -19,7 +19,12 @@ segmentation criterion): the keys of config/specific/midl.yaml (``iic_weight``, 
 ``MineParameters`` builds the MINE baseline (``create_mine_hooks``: one statistics network per feature): ``feature_names``
 and ``weights``, where the reference's old-API ``MineTrainer`` (trainer.py:98-107) reads ``IICRegParameters.weight`` and
 ``FeatureExtractor.feature_names`` / ``feature_importance`` -- ``weights[i] = weight * imp_i / sum(imp)``.  Refused during
-pre-training as well."""
+pre-training as well.
+``PICAConsistencyParams`` builds the PICA baseline (``create_pica_consistency_hook``: the hooks of
+``DiscreteMIConsistencyParams`` with ``PUILoss`` / ``PUISegLoss`` of contrastyou/losses/pica_loss.py as their criteria):
+``feature_names``, ``pica_weights``, ``dense_paddings``, ``consistency_weight`` and ``lamda``.  The reference has the two
+criteria and pairs them with the cluster heads (``PICALossWrapper``, semi_seg/utils.py:242-263) but has no section for them;
+this one follows ``DiscreteMIConsistencyParams`` key for key.  Refused during pre-training like it."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -35,6 +40,7 @@ _SEMI_SECTIONS = (
     ("UCMeanTeacherParameters", "create_uc_mean_teacher_hook", True, True),
     ("MIDLPaperParameters", "create_midl_hook", False, False),
     ("MineParameters", "create_mine_hooks", True, False),
+    ("PICAConsistencyParams", "create_pica_consistency_hook", True, False),
 )
 
 

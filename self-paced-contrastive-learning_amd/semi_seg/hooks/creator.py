@@ -7,7 +7,9 @@ contrast_on) triple combined into one TrainerHook -- and the UDA-IIC factories `
 trainer-registry keys (semi_seg/trainers/__init__.py:11-12).  ``create_uc_mean_teacher_hook`` likewise stands for
 ``UCMeanTeacherTrainer`` (trainer.py:274-290, registry key ``ucmeanteacher``) and ``create_midl_hook`` for ``MIDLTrainer``
 (trainer.py:39-60, registry key ``midl``) and ``create_mine_hooks`` for ``MineTrainer`` (trainer.py:98-107, registry key
-``mine``)."""
+``mine``).  ``create_pica_hooks`` / ``create_pica_consistency_hook`` are the two discrete-MI factories with the PICA criteria
+(contrastyou/losses/pica_loss.py; the reference pairs them with the cluster heads in ``PICALossWrapper``,
+semi_seg/utils.py:242-263, and has no factory of its own for them)."""
 from typing import List, Union
 
 from ...contrastyou.hooks.base import CombineTrainerHook
@@ -19,6 +21,7 @@ from .infonce import INFONCEHook, SelfPacedINFONCEHook, decoder_names
 from .midl import MIDLPaperTrainerHook
 from .mine import MineTrainHook
 from .mt import MeanTeacherTrainerHook
+from .pica import PICATrainHook
 from .ucmt import UCMeanTeacherTrainerHook
 
 
@@ -106,6 +109,33 @@ def create_discrete_mi_consistency_hook(*, model, feature_names: Union[str, List
                                                 model=model)
     consistency_hook = create_consistency_hook(weight=consistency_weight)
     return CombineTrainerHook(discrete_mi_hook, consistency_hook)
+
+
+def create_pica_hooks(*, feature_names: List[str], weights: List[float], paddings: List[int], model, lamda: float = 2.0):
+    """``create_discrete_mi_hooks`` with the PICA criteria: one hook ``pica/<feature>`` per feature, ``paddings`` for the
+    decoder features in their order"""
+    assert len(feature_names) == len(weights), (feature_names, weights)
+    decoder_features = [f for f in feature_names if f in decoder_names]
+    assert len(paddings) == len(decoder_features), (decoder_features, paddings)
+    _pad_gen = iter(paddings)
+    paddings_ = [next(_pad_gen) if f in decoder_features else None for f in feature_names]
+    hooks = [PICATrainHook(name=f"pica/{f.lower()}", model=model, feature_name=f, weight=w, padding=p, lamda=lamda)
+             for f, w, p in zip(feature_names, weights, paddings_)]
+    return CombineTrainerHook(*hooks)
+
+
+def create_pica_consistency_hook(*, model, feature_names: Union[str, List[str]], pica_weights: Union[float, List[float]],
+                                 dense_paddings: List[int] = None, consistency_weight: float, lamda: float = 2.0):
+    """``PICAConsistencyParams``: ``create_discrete_mi_consistency_hook`` with the PICA criteria (and their ``lamda``)"""
+    n_features = 1 if isinstance(feature_names, str) else len(feature_names)
+    pair_generator = ntuple(n_features)
+    feature_names = pair_generator(feature_names)
+    pica_weights = pair_generator(pica_weights)
+    n_dense_features = len([f for f in feature_names if f in decoder_names])
+    dense_paddings = ntuple(n_dense_features)(dense_paddings)
+    pica_hook = create_pica_hooks(feature_names=feature_names, weights=pica_weights, paddings=dense_paddings, model=model,
+                                  lamda=lamda)
+    return CombineTrainerHook(pica_hook, create_consistency_hook(weight=consistency_weight))
 
 
 def create_mean_teacher_hook(*, model, weight: float, alpha: float = 0.999, weight_decay: float = 1e-5, name: str = "mse"):
