@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 22
+#define SPCL_ABI_VERSION 23
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -915,6 +915,24 @@ int spcl_conv_dgrad_poolstats_acc_supported(int dtype, int N, int H, int W, int 
 int spcl_conv3x3_dgrad_poolstats_acc(const void* dy, int dtype, int N, int H, int W, int CinK, int CoutS, const void* w_packed,
                                      void* g, const void* y2, int H2, int W2, const float* scale2, const float* shift2,
                                      const float* mean2, long long* acc, void* stream);
+/* The pooled boundary through the WINDOW-MAXIMUM tensor.  Forward: spcl_bnrelu_pool_forward (bn == NULL: scale / shift) or
+ * spcl_bnrelu_pool_forward_acc (bn != NULL) with one more output, ymax_out [N][H/2][W/2][CS]: per complete 2x2 window and
+ * channel the RAW y of the window's first maximum of fma(scale, y, shift) in scan order (the position max_pool2d's gradient
+ * goes to); act_out may be NULL, pool_out and ymax_out may not.  Backward: spcl_conv3x3_dgrad_poolstats(_acc) with that
+ * tensor, ymax [N][H][W][CoutS] at the dgrad's own resolution, in place of (y2, H2, W2): a quarter of the bytes, one load
+ * and one fma per window where the other form has four and a selection -- g, the rows and the block's words are the same
+ * bits.  Ask the _supported queries first (they imply the _poolstats ones for H2 = 2 H, W2 = 2 W). */
+int spcl_bnrelu_pool_forward_ymax(const void* y, int dtype, int N, int H, int W, int CS, const float* scale,
+                                  const float* shift, const spcl_bn_acc* bn, void* act_out, void* pool_out, void* ymax_out,
+                                  void* stream);
+int spcl_conv_dgrad_poolmax_supported(int dtype, int N, int H, int W, int CinK, int CoutS);
+int spcl_conv3x3_dgrad_poolmax(const void* dy, int dtype, int N, int H, int W, int CinK, int CoutS, const void* w_packed,
+                               void* g, const void* ymax, const float* scale2, const float* shift2, const float* mean2,
+                               float* rows2, void* stream);
+int spcl_conv_dgrad_poolmax_acc_supported(int dtype, int N, int H, int W, int CinK, int CoutS);
+int spcl_conv3x3_dgrad_poolmax_acc(const void* dy, int dtype, int N, int H, int W, int CinK, int CoutS, const void* w_packed,
+                                   void* g, const void* ymax, const float* scale2, const float* shift2, const float* mean2,
+                                   long long* acc, void* stream);
 /* the BatchNorm + ReLU (+ max-pool) backward's apply pass with A, B derived from a backward block in its prologue (no reduction
  * pass where a dgrad filled the block, no finalize launch): exactly one of dact [N][H][W][CS], dpool [N][H/2][W/2][CS]
  * (block already filled) or dact_nc [N][CS] (one value per image and channel: this call's reduction pass fills the block).

@@ -267,6 +267,8 @@ template <> struct Word<float> {
   static constexpr int EPW = 1;
   static __device__ __forceinline__ float get(uint32_t w, int) { return __uint_as_float(w); }
   static __device__ __forceinline__ uint32_t make(const float* v) { return __float_as_uint(v[0]); }
+  // element h of the result = element h of raw word s[h]
+  static __device__ __forceinline__ uint32_t merge(const uint32_t* s) { return s[0]; }
 };
 template <> struct Word<bf16_t> {
   static constexpr int EPW = 2;
@@ -276,6 +278,7 @@ template <> struct Word<bf16_t> {
   static __device__ __forceinline__ uint32_t make(const float* v) {
     return (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
   }
+  static __device__ __forceinline__ uint32_t merge(const uint32_t* s) { return (s[0] & 0x0000ffffu) | (s[1] & 0xffff0000u); }
 };
 
 template <int EPC> __device__ __forceinline__ void load_coef(float* dst, const float* src, int cc) {
@@ -506,11 +509,20 @@ struct Window {
 };
 
 // ---- forward with 2x2 max-pool (act optional)
-template <typename T, bool FAST>
-__global__ __launch_bounds__(256, 4) void bnrelu_fwd_pool_kernel(const T* __restrict__ y, int N, int H, int W, int CS,
+// YMAX: `ymax` [N][H/2][W/2][CS], laid out like `pool`, takes per complete window and channel the RAW y of the window's first
+// maximum of z = fma(scale, y, shift) in scan order (pool_first_max) -- the one value of the window the BatchNorm-backward sums
+// behind a pooled dgrad need (conv_fast.hip MODE 3 finds it again from all four; with this tensor MODE 2 reads it directly).
+// A template parameter, not a null test: the kernel without the side output keeps its instructions.  The selection carries the
+// raw storage WORD of the best position (one select per step, one merge of the halves per word: no conversion back); ACT =
+// false (YMAX forms only: the training blocks that want the side output write no activation) drops the activation words from
+// the register budget -- with them the bf16 kernel sat at the 128 registers of its launch bounds and spilled.
+// (YMAX with ACT -- no caller of the training step, the entry point allows it -- gets the registers of three workgroups per CU.)
+template <typename T, bool FAST, bool YMAX = false, bool ACT = true>
+__global__ __launch_bounds__(256, (YMAX && ACT) ? 3 : 4) void bnrelu_fwd_pool_kernel(const T* __restrict__ y, int N, int H, int W, int CS,
                                                               const float* __restrict__ scale,
                                                               const float* __restrict__ shift, T* __restrict__ act,
-                                                              T* __restrict__ pool, int AS, BnAccFwd bn = BnAccFwd{}) {
+                                                              T* __restrict__ pool, int AS, BnAccFwd bn = BnAccFwd{},
+                                                              T* __restrict__ ymax = nullptr) {
   constexpr int EPC = Chunk<T>::EPC, EPW = Word<T>::EPW;
   const int CPC = CS / EPC, PL = 256 / CPC;
   const int cc = threadIdx.x % CPC, pl = threadIdx.x / CPC;
@@ -534,26 +546,34 @@ __global__ __launch_bounds__(256, 4) void bnrelu_fwd_pool_kernel(const T* __rest
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         if (u == 1 && !second) break;
-        u32x4 mxw, aw[4];
+        u32x4 mxw, aw[4], ymw = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int wi = 0; wi < 4; ++wi) {
-          float mx[EPW], a[4][EPW];
+          float mx[EPW], a[4][EPW], zb[EPW];
+          uint32_t wb[EPW];
 #pragma unroll
           for (int h = 0; h < EPW; ++h) {
             const int e = wi * EPW + h;
             mx[h] = 0.f;  // activations are >= 0
+            zb[h] = 0.f;
+            wb[h] = 0u;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-              a[k][h] = fmaxf(fmaf(sc[e], Word<T>::get(w[u].ry[k][wi], h), sh[e]), 0.f);
+              const float z = fmaf(sc[e], Word<T>::get(w[u].ry[k][wi], h), sh[e]);
+              a[k][h] = fmaxf(z, 0.f);
               if (w[u].valid[k]) mx[h] = fmaxf(mx[h], a[k][h]);
+              if (YMAX) pool_first_max(k, z, w[u].ry[k][wi], zb[h], wb[h]);  // (stored for complete windows only: every k valid)
             }
           }
           mxw[wi] = Word<T>::make(mx);
+          if (YMAX) ymw[wi] = Word<T>::merge(wb);
+          if (ACT) {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) aw[k][wi] = Word<T>::make(a[k]);
+            for (int k = 0; k < 4; ++k) aw[k][wi] = Word<T>::make(a[k]);
+          }
         }
         const int oxu = ox + u * PL;
-        if (act != nullptr) {
+        if (ACT && act != nullptr) {
           // (act may be a channel slice of a wider tensor -- the skip half of a decoder concatenation: AS elements per pixel)
           const size_t a00 = (row0 * W + 2 * oxu) * AS + cc * EPC;
           const size_t aoff[4] = {a00, a00 + AS, a00 + (size_t)W * AS, a00 + (size_t)W * AS + AS};
@@ -563,6 +583,8 @@ __global__ __launch_bounds__(256, 4) void bnrelu_fwd_pool_kernel(const T* __rest
         }
         if (pool != nullptr && (FAST || (oy < OH && oxu < OW)))
           *(u32x4*)(pool + (((size_t)n * OH + oy) * OW + oxu) * CS + cc * EPC) = mxw;
+        if (YMAX && (FAST || (oy < OH && oxu < OW)))
+          *(u32x4*)(ymax + (((size_t)n * OH + oy) * OW + oxu) * CS + cc * EPC) = ymw;
       }
     }
   }
@@ -937,8 +959,7 @@ __global__ __launch_bounds__(256, 3) BWD_POOL_WPE void bnrelu_bwd_pool_kernel(co
 #pragma unroll
               for (int k = 0; k < 4; ++k) {
                 const float yv = Word<T>::get(w.ry[k][wi], h);
-                const float z = w.valid[k] ? fmaf(sc[e], yv, sh[e]) : -1.f;
-                if (k == 0 || z > zb) { zb = z; yb = yv; }
+                pool_first_max(k, w.valid[k] ? fmaf(sc[e], yv, sh[e]) : -1.f, yv, zb, yb);
               }
               const float dzb = (complete && zb > 0.f) ? Word<T>::get(rdp[wi], h) : 0.f;
               s1[e] += dzb;
@@ -1400,7 +1421,8 @@ static thread_local bool tl_acc_fill = false;  // spcl_bnrelu_backward_fill_acc:
 
 template <typename T>
 static int bnrelu_fwd_launch(const void* y, int N, int H, int W, int CS, const float* scale, const float* shift,
-                             void* act, void* pool, hipStream_t st, const BnAccFwd* bnp = nullptr) {
+                             void* act, void* pool, hipStream_t st, const BnAccFwd* bnp = nullptr,
+                             void* ymax = nullptr /* with pool: the window maximum's raw y, laid out like pool */) {
   constexpr int EPC = Chunk<T>::EPC;
   const BnAccFwd bn = bnp != nullptr ? *bnp : BnAccFwd{};
   // (coefficients derived in every workgroup's prologue: fewer, longer-lived workgroups amortise it)
@@ -1409,15 +1431,29 @@ static int bnrelu_fwd_launch(const void* y, int N, int H, int W, int CS, const f
   const int PL = 256 / (CS / EPC);
   const int AS = tl_act_stride > 0 ? tl_act_stride : CS;
   const double tb = (double)N * H * W * CS * sizeof(T);  // bytes of one full-resolution tensor
-  prof_cost(tb * (1.0 + (act != nullptr ? 1.0 : 0.0) + (pool != nullptr ? 0.25 : 0.0)), 0.0);
+  prof_cost(tb * (1.0 + (act != nullptr ? 1.0 : 0.0) + (pool != nullptr ? 0.25 : 0.0) + (ymax != nullptr ? 0.25 : 0.0)), 0.0);
   if (pool != nullptr) {
     const int rows = N * ((H + 1) / 2);
-    if (H % 2 == 0 && W % 2 == 0) {
-      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, true>), dim3(rows < STREAM_MAX_WG ? rows : STREAM_MAX_WG), dim3(256), 0, st, (const T*)y, N, H,
-                       W, CS, scale, shift, (T*)act, (T*)pool, AS, bn);
+    const dim3 grid(rows < STREAM_MAX_WG ? rows : STREAM_MAX_WG);
+    const bool fast = H % 2 == 0 && W % 2 == 0;
+    if (ymax != nullptr && fast && act == nullptr) {
+      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, true, true, false>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift,
+                  (T*)act, (T*)pool, AS, bn, (T*)ymax);
+    } else if (ymax != nullptr && fast) {
+      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, true, true, true>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift,
+                  (T*)act, (T*)pool, AS, bn, (T*)ymax);
+    } else if (ymax != nullptr && act == nullptr) {
+      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, false, true, false>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift,
+                  (T*)act, (T*)pool, AS, bn, (T*)ymax);
+    } else if (ymax != nullptr) {
+      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, false, true, true>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift,
+                  (T*)act, (T*)pool, AS, bn, (T*)ymax);
+    } else if (fast) {
+      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, true>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift, (T*)act,
+                  (T*)pool, AS, bn, (T*)nullptr);
     } else {
-      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, false>), dim3(rows < STREAM_MAX_WG ? rows : STREAM_MAX_WG), dim3(256), 0, st, (const T*)y, N, H,
-                       W, CS, scale, shift, (T*)act, (T*)pool, AS, bn);
+      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, false>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift, (T*)act,
+                  (T*)pool, AS, bn, (T*)nullptr);
     }
   } else {
     const size_t npix = (size_t)N * H * W;
@@ -1738,6 +1774,32 @@ extern "C" int spcl_bnrelu_pool_forward_acc(const void* y, int dtype, int N, int
     return SPCL_EINVAL;
   }
   SPCL_LAUNCH_CHECK("bnrelu_pool_forward_acc");
+  return SPCL_OK;
+}
+
+// spcl_bnrelu_pool_forward / _acc with the window maximum's RAW y as a side output: ymax_out [N][H/2][W/2][CS], per complete
+// window and channel the y of the first maximum of fma(scale, y, shift) in scan order -- what spcl_conv3x3_dgrad_poolmax reads
+// in place of the full-resolution tensor.  bn == NULL: coefficients from scale / shift; else derived from the block (CS <= 256).
+extern "C" int spcl_bnrelu_pool_forward_ymax(const void* y, int dtype, int N, int H, int W, int CS, const float* scale,
+                                             const float* shift, const spcl_bn_acc* bn, void* act_out, void* pool_out,
+                                             void* ymax_out, void* stream) {
+  SPCL_CHECK_ARG(y && pool_out && ymax_out && (bn || (scale && shift)), "bnrelu_pool_forward_ymax: null pointer");
+  SPCL_CHECK_ARG(N > 0 && H >= 2 && W >= 2 && CS > 0 && CS % 16 == 0 && CS <= (bn ? 256 : 1024),
+                 "bnrelu_pool_forward_ymax: bad shape (H, W >= 2; CS <= 256 with an accumulator block)");
+  SPCL_CHECK_ARG(dtype == SPCL_F32 || dtype == SPCL_BF16, "bnrelu_pool_forward_ymax: dtype");
+  BnAccFwd f{};
+  if (bn != nullptr) {
+    SPCL_CHECK_ARG(bn->acc && bn->gamma && bn->beta && bn->st && bn->CS == CS && bn->C > 0 && bn->C <= CS && bn->count >= 1.f,
+                   "bnrelu_pool_forward_ymax: bad accumulator description");
+    f = BnAccFwd{bn->acc, bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->num_batches_tracked, bn->st,
+                 bn->momentum, bn->eps, bn->count, bn->C, bn->CS, 1.0 / (double)bn->count};
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SPCL_F32)
+    bnrelu_fwd_launch<float>(y, N, H, W, CS, scale, shift, act_out, pool_out, st, bn != nullptr ? &f : nullptr, ymax_out);
+  else
+    bnrelu_fwd_launch<bf16_t>(y, N, H, W, CS, scale, shift, act_out, pool_out, st, bn != nullptr ? &f : nullptr, ymax_out);
+  SPCL_LAUNCH_CHECK("bnrelu_pool_forward_ymax");
   return SPCL_OK;
 }
 

@@ -80,6 +80,20 @@ template <> struct Elem<bf16_t> {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// The 2x2 max-pool's selection rule, one scan step: position k = 0 .. 3 of a window with z = fma(scale, y, shift) takes over
+// when it is the first or STRICTLY larger than the best so far (the first maximum in scan order, as torch.max_pool2d; a NaN
+// behind the first position never takes over).  (zb, yb) = the best z and the raw y it came from.  The ONE statement of the
+// rule for the forward's window-maximum side output (bn.hip bnrelu_fwd_pool_kernel), the pooled reduction pass
+// (bnrelu_bwd_pool_kernel) and the pooled dgrad epilogue (conv_fast.hip MODE 3): they must pick the same position.
+// (Y: the value as f32, or the raw storage word that holds it.)
+template <typename Y>
+__device__ __forceinline__ void pool_first_max(int k, float z, Y y, float& zb, Y& yb) {
+  if (k == 0 || z > zb) {
+    zb = z;
+    yb = y;
+  }
+}
+
 // butterfly sum over the 64 lanes of a wave (every lane gets the total; fixed order -> deterministic)
 // (the four steps inside a 16-lane row by DPP moves -- quad swaps, half mirror, mirror: no trips through the LDS crossbar --,
 // the two across rows by shuffles)

@@ -1750,3 +1750,73 @@ static int dgrad_poolstats_impl(const void* dy, int dtype, int N, int H, int W, 
   return SPCL_OK;
 }
 
+// The pooled boundary again, reading the WINDOW-MAXIMUM tensor instead of y2: ymax [N][H][W][CoutS] at the dgrad's own
+// resolution holds, per window and channel, the raw y of the window's first maximum (spcl_bnrelu_pool_forward_ymax -- the
+// position the epilogue above selects from its four loads).  z = fma(scale2, ymax, shift2) from the same coefficients is the
+// zb of that epilogue, so g, the rows and the block's words are the same bits, from a quarter of the bytes: the
+// same-resolution epilogue of spcl_conv3x3_dgrad_bnstats (one prefetched 8-byte load per lane and pixel) in the pooled form's
+// wave / n-tile split.  Offered where the pooled form is.
+static bool dgrad_poolmax_dry(int dtype, int N, int H, int W, int CinK, int CoutS, bool acc) {
+  ConvArgs a;
+  if (!dgrad_bnstats_args(a, dtype, N, H, W, CinK, CoutS) || conv_use_gemm(CinK, CoutS, H, W)) return false;
+  a.x = nullptr; a.y = nullptr; a.wp = nullptr;
+  float dummy;
+  long long dummy2;
+  a.rows2 = &dummy;
+  a.rows2_acc = acc ? &dummy2 : nullptr;
+  a.y2_is_poolmax = true;
+  TileCfg t = pick_tile(H, W);
+  return t.tw == 14 && launch_conv_fast(a, t.th, nullptr, true);
+}
+
+extern "C" int spcl_conv_dgrad_poolmax_supported(int dtype, int N, int H, int W, int CinK, int CoutS) {
+  if (!spcl_conv_dgrad_poolstats_supported(dtype, N, H, W, CinK, CoutS, 2 * H, 2 * W)) return 0;
+  return dgrad_poolmax_dry(dtype, N, H, W, CinK, CoutS, false) ? 1 : 0;
+}
+
+extern "C" int spcl_conv_dgrad_poolmax_acc_supported(int dtype, int N, int H, int W, int CinK, int CoutS) {
+  if (!spcl_conv_dgrad_poolstats_acc_supported(dtype, N, H, W, CinK, CoutS, 2 * H, 2 * W)) return 0;
+  return dgrad_poolmax_dry(dtype, N, H, W, CinK, CoutS, true) ? 1 : 0;
+}
+
+static int dgrad_poolmax_impl(const void* dy, int dtype, int N, int H, int W, int CinK, int CoutS, const void* w_packed,
+                              void* g, const void* ymax, const float* scale2, const float* shift2, const float* mean2,
+                              float* rows2, long long* acc, void* stream) {
+  SPCL_CHECK_ARG(dy && w_packed && g && ymax && scale2 && shift2 && mean2, "conv3x3_dgrad_poolmax: null pointer");
+  ConvArgs a;
+  if (!dgrad_bnstats_args(a, dtype, N, H, W, CinK, CoutS) || conv_use_gemm(CinK, CoutS, H, W)) {
+    set_error("conv3x3_dgrad_poolmax: unsupported configuration");
+    return SPCL_EUNSUPPORTED;
+  }
+  a.x = dy; a.y = g; a.wp = w_packed;
+  a.y2 = ymax; a.scale2 = scale2; a.shift2 = shift2; a.mean2 = mean2;
+  a.rows2 = acc != nullptr ? (float*)acc : rows2;  // (with a block: only the mode marker, never written)
+  a.rows2_acc = acc;
+  a.y2_is_poolmax = true;
+  hipStream_t st = (hipStream_t)stream;
+  const double px = (double)N * H * W;
+  prof_cost(px * (CinK + 2.0 * CoutS) * 2.0 + 9.0 * CinK * CoutS * 2.0, 2.0 * px * 9.0 * CinK * CoutS);  // (ymax: one CoutS per pixel)
+  TileCfg t = pick_tile(H, W);
+  if (!(t.tw == 14 && launch_conv_fast(a, t.th, st))) {
+    set_error("conv3x3_dgrad_poolmax: no specialised kernel for H=%d W=%d CinK=%d CoutS=%d", H, W, CinK, CoutS);
+    return SPCL_EUNSUPPORTED;
+  }
+  SPCL_LAUNCH_CHECK("conv3x3_dgrad_poolmax");
+  return SPCL_OK;
+}
+
+extern "C" int spcl_conv3x3_dgrad_poolmax(const void* dy, int dtype, int N, int H, int W, int CinK, int CoutS,
+                                          const void* w_packed, void* g, const void* ymax, const float* scale2,
+                                          const float* shift2, const float* mean2, float* rows2, void* stream) {
+  SPCL_CHECK_ARG(rows2, "conv3x3_dgrad_poolmax: null pointer");
+  return dgrad_poolmax_impl(dy, dtype, N, H, W, CinK, CoutS, w_packed, g, ymax, scale2, shift2, mean2, rows2, nullptr, stream);
+}
+
+// ... with the sums added to a fixed-point accumulator block (see spcl_conv3x3_dgrad_bnstats_acc)
+extern "C" int spcl_conv3x3_dgrad_poolmax_acc(const void* dy, int dtype, int N, int H, int W, int CinK, int CoutS,
+                                              const void* w_packed, void* g, const void* ymax, const float* scale2,
+                                              const float* shift2, const float* mean2, long long* acc, void* stream) {
+  SPCL_CHECK_ARG(acc, "conv3x3_dgrad_poolmax_acc: null pointer");
+  return dgrad_poolmax_impl(dy, dtype, N, H, W, CinK, CoutS, w_packed, g, ymax, scale2, shift2, mean2, nullptr, acc, stream);
+}
+

@@ -47,6 +47,10 @@ struct ConvArgs {
   // ... or, with H2 > 0, of the POOLED layer: y2 is [N][H2][W2][CoutS] at twice the resolution (H == H2 / 2), the dgrad's
   // output is the gradient of maxpool2x2(relu(bn(y2)))
   int H2 = 0, W2 = 0;
+  // ... or, pooled likewise, with y2 the WINDOW-MAXIMUM tensor the pooled forward left ([N][H][W][CoutS], the raw y of each
+  // window's first maximum: spcl_bnrelu_pool_forward_ymax) and H2 == 0: the same-resolution epilogue (MODE 2) reads one value
+  // where the form above reads four and selects; the wave / n-tile split is the pooled form's, so both leave the same bits
+  bool y2_is_poolmax = false;
   // ... and, for the block whose first conv reads a ONE-CHANNEL f32 image (unet.py:123), the nine sums
   // sum_p dz[p][co] img[p + tap] of that conv's weight gradient as rows 2 .. 10 of rows2 ([tile][11][CoutS], MODE 4)
   const float* img2 = nullptr;

@@ -38,6 +38,8 @@ struct FastArgs {
   const float* mean2;
   float* rows2;             // [tile][2][CoutS]: sum dz, sum dz (y2 - mean)
   // MODE 3 (dgrad whose output g is the gradient of maxpool2x2(relu(bn(y2)))): y2 is [N][H2][W2][CoutS], H = H2 / 2
+  // (where the pooled forward left the window maxima -- ConvArgs::y2_is_poolmax -- that tensor IS a same-resolution y2: the
+  // launch is MODE 2 with H2 == 0, in MODE 3's wave / n-tile split; MODE 3 remains the form for callers without it)
   int H2, W2;
   // MODE 4 (= MODE 2 for the layer behind a one-channel f32 image): rows2 is [tile][11][CoutS]; rows 2 .. 10 hold
   // sum_p dz[p][co] img[p + tap], the data-dependent part of that layer's weight gradient (dy = scale dz + A y + B: the
@@ -807,11 +809,7 @@ conv3x3_fast_kernel(FastArgs a) {
             for (int k = 0; k < 4; ++k) {
               const uint32_t wd = r < 2 ? yr[k].x : yr[k].y;
               const float yv = (r & 1) ? __uint_as_float(wd & 0xffff0000u) : __uint_as_float(wd << 16);
-              const float z = fmaf(sc2[j][r], yv, sh2[j][r]);
-              if (k == 0 || z > zb) {
-                zb = z;
-                yb = yv;
-              }
+              pool_first_max(k, fmaf(sc2[j][r], yv, sh2[j][r]), yv, zb, yb);
             }
             const float dz = zb > 0.f ? gv[r] * keep : 0.f;
             ssum[j][r] += dz;
@@ -1242,7 +1240,8 @@ bool launch_conv_fast(const ConvArgs& c, int th, hipStream_t st, bool dry) {
   // 42.9 -> 38.6 us as two waves of 140: 2 = that form only, the default)
   static const int env_narrow = lab_env("SPCL_CONV_FAST_NARROW_NT1", 2);
   if (env_narrow == 1 && KC < 64 && ntn == 2 && th == 7) NT = 1;
-  if (env_narrow == 2 && KC == 32 && ntn == 2 && th == 7 && c.rows2 != nullptr && c.H2 == 0 && c.img2 == nullptr) NT = 1;
+  if (env_narrow == 2 && KC == 32 && ntn == 2 && th == 7 && c.rows2 != nullptr && c.H2 == 0 && !c.y2_is_poolmax && c.img2 == nullptr)
+    NT = 1;
   int nw = ntn / NT;
   if (nw > 4) nw = 4;
   if (ntn % (NT * nw) != 0) return false;

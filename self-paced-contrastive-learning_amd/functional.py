@@ -882,10 +882,13 @@ class PoolLink:
     epilogue of its own input-gradient kernel (spcl_conv3x3_dgrad_poolstats): this block's raw second-conv output and BN
     coefficients.  The next block fills ``rows`` / ``dx_ptr``; this block's backward uses them if the pooled gradient it
     receives IS that kernel's output (same storage: nothing else contributed to it), else runs its own reduction pass."""
-    __slots__ = ("yb", "stb", "N", "H", "W", "cout_s", "rows", "dx_ptr", "holder", "version", "acc")
+    __slots__ = ("yb", "stb", "N", "H", "W", "cout_s", "rows", "dx_ptr", "holder", "version", "acc", "ymax")
 
-    def __init__(self, yb, stb, N, H, W, cout_s, acc=None):
+    def __init__(self, yb, stb, N, H, W, cout_s, acc=None, ymax=None):
         self.yb, self.stb, self.N, self.H, self.W, self.cout_s = yb, stb, N, H, W, cout_s
+        # ``ymax``: [N, H/2, W/2, cout_s], the raw ``yb`` at each pooling window's first maximum (the pooled forward's side
+        # output, ``_pool_ymax_pays``): the next block's dgrad reads it instead of ``yb`` (spcl_conv3x3_dgrad_poolmax)
+        self.ymax = ymax
         # ``acc``: a zeroed fixed-point accumulator block (bn_acc_block) the next block's dgrad may ADD the sums to instead of
         # writing per-tile rows; ``rows`` is then ``ACC_ROWS`` and the apply pass derives its coefficients from the block
         self.acc = acc
@@ -896,6 +899,24 @@ class PoolLink:
     def fresh(self, ptr):
         """is the gradient at ``ptr`` exactly the tensor the producer left (same storage, never accumulated into in place)?"""
         return self.rows is not None and ptr == self.dx_ptr and self.holder is not None and self.holder._version == self.version
+
+
+def _pool_ymax_pays(N, H, W, cout_s):
+    """Does the pooled forward of a block with raw output [N, H, W, cout_s] leave the window-maximum tensor for the next block's
+    dgrad?  It pays where the dgrad's saved reads (3/4 of ``yb``) outweigh the extra 1/4-size store of the pooled forward.
+    Measured per launch inside the replayed pre-train step (N = 64 bf16, one MI355X, parent -> this form, us;
+    profiles/poolmax_timeline_{parent,branch}.txt):
+
+        yb [N, H, W, C]          bytes      pooled forward     next block's dgrad    net
+        64 x 224 x 224 x  16   102.8 MB     21.9 -> 25.6        37.0 -> 26.7        -6.6
+        64 x 112 x 112 x  32    51.4 MB     11.6 -> 14.0        28.2 -> 24.4        -1.4
+        64 x  56 x  56 x  64    25.7 MB      8.2 ->  9.0        18.9 -> 15.0        -3.1
+        64 x  28 x  28 x 128    12.8 MB      6.3 ->  6.8        17.5 -> 13.9        -3.1
+
+    Every measured level gains, so the rule is their range: from the smallest measured tensor up.  Below it nothing was
+    measured (a tensor of a few MB is still in cache when the dgrad reads it: there is little traffic to save) and the
+    full-tensor form stays."""
+    return N * H * W * cout_s * 2 >= 12 * 2 ** 20
 
 
 class ActLink:
@@ -928,7 +949,7 @@ class BlockCfg:
     """Static configuration of one fused Conv-BN-ReLU(-Conv-BN-ReLU)(-MaxPool) block call."""
     __slots__ = ("dtype", "training", "momentum", "eps", "track", "need_act", "need_pool", "image_input", "buffers",
                  "link_in", "link_out", "act_dst", "up2", "lazy_act", "link_act", "x2_link", "bn_link", "x2_bn", "up_in", "up_link",
-                 "gap", "want_gap")
+                 "gap", "want_gap", "grad_mode")
 
     def __init__(self, dtype, training, momentum, eps, track, need_act, need_pool, image_input, buffers):
         self.dtype, self.training, self.momentum, self.eps, self.track = dtype, training, momentum, eps, track
@@ -946,6 +967,8 @@ class BlockCfg:
         self.x2_bn = None      # ... conv_block(..., x2=that activation): its dgrad leaves that BatchNorm's backward sums there
         self.gap = None       # set by the forward: [N, C] f32 global average of the activation it wrote (small maps), see conv_block
         self.want_gap = False  # the caller has a consumer for it (the block's output is tapped by a forward hook: semi_seg/arch/hook.py)
+        self.grad_mode = True  # set by conv_block: was autograd recording at the call?  (``needs_input_grad`` alone says "yes" under
+                               # torch.no_grad() too; side outputs that only a backward reads are not written then)
         self.up2 = False      # the activation's only consumer is nn.Upsample(scale_factor=2): write it 2x2-replicated, return
                               # the [N, C, 2H, 2W] tensor (spcl_bnrelu_up2_forward); backward sums the 2x2 gradients first
 
@@ -1823,6 +1846,12 @@ class _ConvBlockFn(torch.autograd.Function):
         want_gap = (_GAP and getattr(cfg, "want_gap", False) and cfg.need_act and not cfg.need_pool and not lazy
                     and not ctx.up2 and cfg.act_dst is None
                     and H * W <= 1024 and _n.call("spcl_bnrelu_gap_supported", dtc, H, W, cout, cout_s))
+        # a training block whose ONLY product is the pooled activation offers the next block a PoolLink (below): its writer then also
+        # leaves the window maxima's raw values where that pays (training with a backward only: eval / inference write nothing)
+        offers_link = need_bwd and cfg.need_pool and not cfg.need_act and cfg.training and dtype == torch.bfloat16
+        want_ymax = (offers_link and cfg.grad_mode and not want_gap and not lazy and not ctx.up2 and H >= 2 and W >= 2
+                     and _pool_ymax_pays(N, H, W, cout_s))
+        ymax = None
         if want_gap:
             act, pool = torch.empty(N, H, W, cout_s, dtype=dtype, device=dev), None
             cfg.gap = torch.empty(N, cout, dtype=torch.float32, device=dev)
@@ -1832,8 +1861,13 @@ class _ConvBlockFn(torch.autograd.Function):
         elif use_b:
             act = torch.empty(N, H, W, cout_s, dtype=dtype, device=dev) if cfg.need_act else None
             pool = torch.empty(N, H // 2, W // 2, cout_s, dtype=dtype, device=dev) if cfg.need_pool else None
-            _n.call("spcl_bnrelu_pool_forward_acc", _n.ptr(yb), dtc, N, H, W, cout_s, ctypes.byref(bn_b), _n.ptr(act),
-                    _n.ptr(pool), _n.stream())
+            if want_ymax:
+                ymax = torch.empty_like(pool)
+                _n.call("spcl_bnrelu_pool_forward_ymax", _n.ptr(yb), dtc, N, H, W, cout_s, None, None, ctypes.byref(bn_b),
+                        None, _n.ptr(pool), _n.ptr(ymax), _n.stream())
+            else:
+                _n.call("spcl_bnrelu_pool_forward_acc", _n.ptr(yb), dtc, N, H, W, cout_s, ctypes.byref(bn_b), _n.ptr(act),
+                        _n.ptr(pool), _n.stream())
         elif lazy:
             # no activation tensor: the consumer (conv1x1_bn) reads yb and applies scale / shift / ReLU in its loader
             act, pool = yb, None
@@ -1846,14 +1880,19 @@ class _ConvBlockFn(torch.autograd.Function):
         else:
             act = _act_buffer(cfg, N, H, W, cout_s, dtype, dev) if cfg.need_act else None
             pool = torch.empty(N, H // 2, W // 2, cout_s, dtype=dtype, device=dev) if cfg.need_pool else None
-            _bnrelu_fwd(yb, dtc, N, H, W, cout_s, stb[2], stb[3], act, pool)
+            if want_ymax:
+                ymax = torch.empty_like(pool)
+                _n.call("spcl_bnrelu_pool_forward_ymax", _n.ptr(yb), dtc, N, H, W, cout_s, _n.ptr(stb[2]), _n.ptr(stb[3]), None,
+                        None, _n.ptr(pool), _n.ptr(ymax), _n.stream())
+            else:
+                _bnrelu_fwd(yb, dtc, N, H, W, cout_s, stb[2], stb[3], act, pool)
         ctx.save_for_backward(xs, ya, yb, sta, stb, wa, wb)
         ctx.x2s = x2s  # (not an input of this Function as a tensor object: a detached re-layout, kept directly)
         ctx.params = (wa, ga, ba, wb, gb, bb)
         ctx.packed_t = (wpa_t, wpb_t)
         ctx.cfg = cfg
         if need_bwd and pool is not None and act is None and cfg.training and dtype == torch.bfloat16:
-            cfg.link_out = PoolLink(yb, stb, N, H, W, cout_s, ctx.acc_bwd_b)  # the pooled output is this block's only product
+            cfg.link_out = PoolLink(yb, stb, N, H, W, cout_s, ctx.acc_bwd_b, ymax)  # the pooled output is this block's only product
         ctx.meta = (N, cin, H, W, cout, cout_s, cin_s, cin_k, mode_a, x.dtype)
         outs = []
         outs.append(nhwc_to_logical(act, cout) if act is not None else None)
@@ -2039,24 +2078,38 @@ class _ConvBlockFn(torch.autograd.Function):
             if (li is not None and dtype == torch.bfloat16 and li.cout_s == cin_s and li.N == N
                     and _n.call("spcl_conv_dgrad_poolstats_supported", dtc, N, H, W, cout_s, cin_s, li.H, li.W)):
                 dxs = torch.empty(N, H, W, cin_s, dtype=dtype, device=dya.device)
+                # the producer's pooled forward left the window maxima (``_pool_ymax_pays``): the epilogue reads that tensor, a
+                # quarter of ``li.yb``'s bytes, and leaves the same bits (spcl_conv3x3_dgrad_poolmax)
+                ym = li.ymax if (li.ymax is not None and tuple(li.ymax.shape) == (N, H, W, cin_s)) else None
                 if (li.acc is not None and _n.call("spcl_conv_dgrad_poolstats_acc_supported", dtc, N, H, W, cout_s, cin_s,
                                                    li.H, li.W)):
                     # ... added to the producing block's accumulator block (zeroed with its forward): no rows, no finalize.
                     # Taken ONCE, like ``_take_acc``: the block is zero only for the first backward after its forward; a second
                     # backward through the same graph (retain_graph=True) finds None here and writes rows
                     acc_in, li.acc = li.acc, None
-                    _n.call("spcl_conv3x3_dgrad_poolstats_acc", _n.ptr(dya), dtc, N, H, W, cout_s, cin_s, _n.ptr(wpa_t),
-                            _n.ptr(dxs), _n.ptr(li.yb), li.H, li.W, _n.ptr(li.stb[2]), _n.ptr(li.stb[3]), _n.ptr(li.stb[0]),
-                            _n.ptr(acc_in), _n.stream())
+                    if ym is not None and _n.call("spcl_conv_dgrad_poolmax_acc_supported", dtc, N, H, W, cout_s, cin_s):
+                        _n.call("spcl_conv3x3_dgrad_poolmax_acc", _n.ptr(dya), dtc, N, H, W, cout_s, cin_s, _n.ptr(wpa_t),
+                                _n.ptr(dxs), _n.ptr(ym), _n.ptr(li.stb[2]), _n.ptr(li.stb[3]), _n.ptr(li.stb[0]),
+                                _n.ptr(acc_in), _n.stream())
+                    else:
+                        _n.call("spcl_conv3x3_dgrad_poolstats_acc", _n.ptr(dya), dtc, N, H, W, cout_s, cin_s, _n.ptr(wpa_t),
+                                _n.ptr(dxs), _n.ptr(li.yb), li.H, li.W, _n.ptr(li.stb[2]), _n.ptr(li.stb[3]),
+                                _n.ptr(li.stb[0]), _n.ptr(acc_in), _n.stream())
                     rows = ACC_ROWS
                 else:
                     nt = _n.call("spcl_conv_stat_rows", dtc, N, H, W, cout_s, cin_s)
                     rows = torch.empty(nt * 2 * cin_s, dtype=torch.float32, device=dya.device)
-                    _n.call("spcl_conv3x3_dgrad_poolstats", _n.ptr(dya), dtc, N, H, W, cout_s, cin_s, _n.ptr(wpa_t),
-                            _n.ptr(dxs), _n.ptr(li.yb), li.H, li.W, _n.ptr(li.stb[2]), _n.ptr(li.stb[3]), _n.ptr(li.stb[0]),
-                            _n.ptr(rows), _n.stream())
+                    if ym is not None and _n.call("spcl_conv_dgrad_poolmax_supported", dtc, N, H, W, cout_s, cin_s):
+                        _n.call("spcl_conv3x3_dgrad_poolmax", _n.ptr(dya), dtc, N, H, W, cout_s, cin_s, _n.ptr(wpa_t),
+                                _n.ptr(dxs), _n.ptr(ym), _n.ptr(li.stb[2]), _n.ptr(li.stb[3]), _n.ptr(li.stb[0]),
+                                _n.ptr(rows), _n.stream())
+                    else:
+                        _n.call("spcl_conv3x3_dgrad_poolstats", _n.ptr(dya), dtc, N, H, W, cout_s, cin_s, _n.ptr(wpa_t),
+                                _n.ptr(dxs), _n.ptr(li.yb), li.H, li.W, _n.ptr(li.stb[2]), _n.ptr(li.stb[3]),
+                                _n.ptr(li.stb[0]), _n.ptr(rows), _n.stream())
                     rows.ntiles = nt
                 li.rows, li.dx_ptr, li.holder, li.version = rows, dxs.data_ptr(), dxs, dxs._version
+                li.ymax = None  # (its one reader has run: a second backward through the graph reads ``li.yb``, same bits)
             split = None
             if (dxs is None and x2s is not None and _CONV_SPLIT
                     and _n.call("spcl_conv_split_supported", dtc, N, H, W, cout_s, cin_s)):
@@ -2104,6 +2157,7 @@ class _ConvBlockFn(torch.autograd.Function):
 
 def conv_block(x, wa, ga, ba, wb, gb, bb, cfg: BlockCfg, x2=None):
     """-> (act or None, pooled or None), logical NCHW views over NHWC storage.  ``x2``: see ``_ConvBlockFn.forward``."""
+    cfg.grad_mode = torch.is_grad_enabled()
     act, pool = _ConvBlockFn.apply(x, wa, ga, ba, wb, gb, bb, cfg, x2)
     gap = getattr(cfg, "gap", None)
     if gap is not None and act is not None:
