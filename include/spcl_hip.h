@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 23
+#define SPCL_ABI_VERSION 24
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -840,6 +840,19 @@ int spcl_augment_views_recipe_ws(const float* src, const unsigned char* labels, 
 int spcl_resize_bilinear_pil(const float* src, int S, int HS, int WS, const int* bounds_x, const int* kk_x, int ksize_x,
                              const int* bounds_y, const int* kk_y, int ksize_y, float* tmp, float* out, int OH, int OW,
                              void* stream);
+/* Image.resize((OW, OH), NEAREST) of every slice of a u8 label store [S][HS][WS] -> out [S][OH][OW]: what Resize(224)
+ * (semi_seg/augment.py:57,74,86) does to a TARGET, for which the reference's wrapper swaps the common transform's
+ * interpolation to NEAREST (contrastyou/augment/synchronize.py:105-107).  out[s][y][x] = src[s][ytab[y]][xtab[x]]; the
+ * caller precomputes one int32 source-index table per axis on the host by PIL's own rule -- the ACCUMULATED form
+ * xo = scale / 2; tab[x] = (int)xo; xo += scale with scale = n_in / n_out in double, NOT (x + 0.5) * scale, which differs
+ * from PIL in places (semi_seg/data/augment.py nearest_resize_table).  The caller keeps every entry inside [0, n_in); as a
+ * defence the kernel clamps an entry into that range (a wrong table then gives a wrong pixel of the same slice, never a
+ * read outside the store).  One thread writes 16 neighbouring output bytes of a row with one 128-bit store where
+ * OW % 16 == 0 and `out` is 16-byte aligned, 4 bytes with one 32-bit store where OW % 4 == 0 and `out` is 4-byte aligned,
+ * single bytes otherwise; src needs no alignment.  SPCL_EINVAL: a null pointer, a non-positive shape,
+ * S * OH * OW >= 2^31.  (ABI 24) */
+int spcl_resize_nearest_pil(const unsigned char* src, int S, int HS, int WS, const int* xtab /*[OW]*/,
+                            const int* ytab /*[OH]*/, unsigned char* out, int OH, int OW, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Per-sample random flips of an NCHW batch (TensorRandomFlip(axis=[1,2], threshold=0.8), new_epocher.py:112, applied

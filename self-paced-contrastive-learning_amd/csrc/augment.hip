@@ -426,9 +426,62 @@ __global__ __launch_bounds__(256) void resize_pass_kernel(const float* __restric
   dst[img * img_stride_out + (size_t)line * line_stride_out + (size_t)xx * elem_stride_out] = __fdiv_rn((float)q, 255.f);
 }
 
+// Image.resize((OW, OH), NEAREST) of u8 label maps (Geometry.c nearest_resize via ImagingScaleAffine; what the reference's
+// wrapper selects for targets, contrastyou/augment/synchronize.py:105-107, under Resize(224) of semi_seg/augment.py:57,74,86):
+// out[s][y][x] = src[s][ytab[y]][xtab[x]] with the per-axis source indices the host accumulated as PIL does.  A gather of
+// one byte per output byte and nothing else.  One thread owns PACK neighbouring output bytes of a row and writes them with ONE
+// store: 16 bytes (128 bits) where OW % 16 == 0 and `out` is 16-byte aligned, 4 bytes (32 bits) where OW % 4 == 0 and `out`
+// is 4-byte aligned -- either makes every row base as aligned as `out` --, single bytes otherwise.  Index arithmetic in 32
+// bits (S * OH * OW < 2^31).  The source bytes of neighbouring outputs are neighbours or the same byte of one source row.
+// Table entries are clamped into the source (a wrong table reads a wrong pixel of the same slice, never another allocation).
+template <int PACK>
+__global__ __launch_bounds__(256) void resize_nearest_kernel(const unsigned char* __restrict__ src, unsigned total, int HS,
+                                                            int WS, const int* __restrict__ xtab,
+                                                            const int* __restrict__ ytab, unsigned char* __restrict__ out,
+                                                            int OH, int OW) {
+  const unsigned units = (unsigned)OW / PACK;  // per output row
+  const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+  if (idx >= total) return;  // total = S * OH * units
+  const unsigned line = idx / units, u = idx - line * units;  // line = s * OH + y
+  const unsigned s = line / (unsigned)OH, y = line - s * (unsigned)OH;
+  const int sy = min(max(ytab[y], 0), HS - 1);
+  const unsigned char* in = src + ((size_t)s * HS + sy) * (size_t)WS;
+  unsigned char* o = out + (size_t)line * OW + PACK * u;
+  if constexpr (PACK == 1) {
+    o[0] = in[min(max(xtab[u], 0), WS - 1)];
+  } else {
+    uint32_t w[PACK / 4] = {};
+#pragma unroll
+    for (int k = 0; k < PACK; ++k) w[k / 4] |= (uint32_t)in[min(max(xtab[PACK * u + k], 0), WS - 1)] << (8 * (k % 4));
+    if constexpr (PACK == 16) *reinterpret_cast<uint4*>(o) = make_uint4(w[0], w[1], w[2], w[3]);
+    else *reinterpret_cast<uint32_t*>(o) = w[0];
+  }
+}
+
 }  // namespace spcl
 
 using namespace spcl;
+
+extern "C" int spcl_resize_nearest_pil(const unsigned char* src, int S, int HS, int WS, const int* xtab, const int* ytab,
+                                       unsigned char* out, int OH, int OW, void* stream) {
+  SPCL_CHECK_ARG(src && xtab && ytab && out, "resize_nearest_pil: null pointer");
+  SPCL_CHECK_ARG(S > 0 && HS > 0 && WS > 0 && OH > 0 && OW > 0, "resize_nearest_pil: bad shape (%d x %dx%d -> %dx%d)", S, HS,
+                 WS, OH, OW);
+  SPCL_CHECK_ARG((long long)S * OH * OW < (1LL << 31), "resize_nearest_pil: %d x %dx%d output bytes: 2^31 or more", S, OH, OW);
+  hipStream_t st = (hipStream_t)stream;
+  const int pack = (OW % 16 == 0 && (uintptr_t)out % 16 == 0) ? 16 : (OW % 4 == 0 && (uintptr_t)out % 4 == 0) ? 4 : 1;
+  const unsigned total = (unsigned)S * (unsigned)OH * (unsigned)(OW / pack);
+  const dim3 grid((total + 255) / 256);
+  if (pack == 16) {
+    SPCL_LAUNCH(resize_nearest_kernel<16>, grid, dim3(256), 0, st, src, total, HS, WS, xtab, ytab, out, OH, OW);
+  } else if (pack == 4) {
+    SPCL_LAUNCH(resize_nearest_kernel<4>, grid, dim3(256), 0, st, src, total, HS, WS, xtab, ytab, out, OH, OW);
+  } else {
+    SPCL_LAUNCH(resize_nearest_kernel<1>, grid, dim3(256), 0, st, src, total, HS, WS, xtab, ytab, out, OH, OW);
+  }
+  SPCL_LAUNCH_CHECK("resize_nearest_pil");
+  return SPCL_OK;
+}
 
 extern "C" int spcl_augment_views_recipe(const float* src, const unsigned char* labels, int S, int HS, int WS,
                                          const int* params, int nviews, float* out, long long* label_out, int OH, int OW,

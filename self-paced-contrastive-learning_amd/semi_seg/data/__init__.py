@@ -4,7 +4,8 @@ as one HIP launch per batch instead of PIL in DataLoader workers."""
 from .rearr import ContrastBatchSampler, ContrastDataset  # noqa: F401
 from .dataset import (ACDCSliceStore, DeviceSliceStore, ProstateSliceStore, acdc_partition, prostate_partition,  # noqa: F401
                       synthetic_slice_store)
-from .augment import RECIPES, PretrainViews, RecipeViews, draw_view_params, resize_store  # noqa: F401
+from .augment import (RECIPES, PretrainViews, RecipeViews, draw_view_params, nearest_resize_table, resize_labels,  # noqa: F401
+                      resize_store)
 from .loader import (ContrastiveDeviceLoader, InfiniteRandomSampler, LabeledDeviceLoader,  # noqa: F401
                      get_contrastive_dataloader)
 from .creator import (ScanBatchLoader, ScanBatchSampler, UnlabeledDeviceLoader, get_data, register_dataset,  # noqa: F401

@@ -228,11 +228,11 @@ def resize_shorter_edge(hw, size: int):
 
 def resize_store(images: torch.Tensor, size: int) -> torch.Tensor:
     """``transforms.Resize(size)`` (bilinear, PIL's arithmetic) of every slice of an 8-bit store [S, H, W] -> [S, oh, ow]"""
-    _n.require_gpu(images)
     S, HS, WS = images.shape
     oh, ow = resize_shorter_edge((HS, WS), size)
     if (oh, ow) == (HS, WS):
         return images
+    _n.require_gpu(images)
     bx, kx, ksx = resize_coeffs(WS, ow)
     by, ky, ksy = resize_coeffs(HS, oh)
     dev = images.device
@@ -246,19 +246,63 @@ def resize_store(images: torch.Tensor, size: int) -> torch.Tensor:
     return out
 
 
+def nearest_resize_table(n_in: int, n_out: int):
+    """the source index of every output pixel along one axis of ``Image.resize(.., NEAREST)`` (Geometry.c ImagingScaleAffine:
+    ``xo = a2 + a0 * 0.5``, then ``xintab[x] = (int) xo; xo += a0`` with a0 = n_in / n_out in double).  The ACCUMULATED sum is
+    the rule: the closed form ``int((x + 0.5) * scale)`` rounds differently and picks the neighbouring pixel in places
+    (tests/test_prostate_host.py keeps a case)."""
+    scale = n_in / n_out
+    xo = scale * 0.5
+    tab = []
+    for _ in range(n_out):
+        tab.append(int(xo))
+        xo += scale
+    if tab and not (0 <= min(tab) and max(tab) < n_in):
+        raise ValueError(f"nearest_resize_table({n_in}, {n_out}): a source index outside [0, {n_in})")
+    return tab
+
+
+def resize_labels(targets: torch.Tensor, size: int) -> torch.Tensor:
+    """``transforms.Resize(size)`` of every u8 label map of a store [S, H, W] -> [S, oh, ow] with NEAREST, as the reference's
+    wrapper resizes a target (contrastyou/augment/synchronize.py:105-107); the shape ``resize_store`` gives the images.
+    Returns its argument when the maps already have that shape."""
+    S, HS, WS = targets.shape
+    oh, ow = resize_shorter_edge((HS, WS), size)
+    if (oh, ow) == (HS, WS):
+        return targets
+    _n.require_gpu(targets)
+    if targets.dtype != torch.uint8:
+        raise TypeError(f"resize_labels: label maps are uint8 class codes, got {targets.dtype}")
+    xtab, ytab = nearest_resize_table(WS, ow), nearest_resize_table(HS, oh)
+    src = targets.contiguous()
+    tx, ty = _upload_tables(xtab, ytab, src.device)
+    out = torch.empty(S, oh, ow, dtype=torch.uint8, device=src.device)
+    _n.call("spcl_resize_nearest_pil", _n.ptr(src), S, HS, WS, _n.ptr(tx), _n.ptr(ty), _n.ptr(out), oh, ow, _n.stream())
+    return out
+
+
+def _upload_tables(xtab, ytab, device):
+    both = torch.tensor(list(xtab) + list(ytab), dtype=torch.int32).to(device)
+    return both[:len(xtab)], both[len(xtab):]
+
+
 class RecipeViews:
     """views of a device store by one of ``RECIPES`` (or a dict of the same keys): ``pairs(indices)`` -> two INDEPENDENT
     views per slice (SequentialWrapperTwice(total_freedom=True): the pre-train recipes); ``labelled(indices)`` -> ONE geometry
     per slice applied to image (bilinear) and label map (nearest) -- the `label` recipes, whose two returned versions share
     the common seed and have no image-only randomness: they are the same tensors twice."""
 
-    def __init__(self, images: torch.Tensor, recipe="acdc_pretrain", out_hw=(224, 224), labels: torch.Tensor = None):
-        _n.require_gpu(images)
+    def __init__(self, images: torch.Tensor, recipe="acdc_pretrain", out_hw=(224, 224), labels: torch.Tensor = None,
+                 resized_to=None):
+        """``resized_to``: the size the store was resized to when it was built (``DeviceSliceStore.resized``): a recipe whose
+        ``resize`` is that size finds its work done.  Otherwise the recipe's ``Resize`` happens here, once: images BILINEAR,
+        label maps NEAREST."""
         self.recipe = dict(RECIPES[recipe]) if isinstance(recipe, str) else dict(recipe)
-        if self.recipe.get("resize"):
-            images = resize_store(images, int(self.recipe["resize"]))
+        size = self.recipe.get("resize")
+        if size and resized_to != int(size):
+            images = resize_store(images, int(size))
             if labels is not None:
-                raise NotImplementedError("label maps are resized with NEAREST by the reference: resize them before building the store")
+                labels = resize_labels(labels.to(torch.uint8), int(size))
         self.images, self.out_hw = images.float().contiguous(), tuple(out_hw)
         self.labels = labels.to(torch.uint8).contiguous() if labels is not None else None
 
@@ -267,6 +311,7 @@ class RecipeViews:
         return [draw_recipe_params(i, hw, self.out_hw, self.recipe, rng) for i in indices]
 
     def apply(self, rows, with_labels=False):
+        _n.require_gpu(self.images, self.labels)
         S, HS, WS = self.images.shape
         oh, ow = self.out_hw
         dev = self.images.device

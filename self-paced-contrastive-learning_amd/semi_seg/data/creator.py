@@ -50,6 +50,10 @@ _FACTORIES: Dict[str, Callable[[str], DeviceSliceStore]] = {}
 _DATA_ROOT = [os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))),
                            ".data")]  # contrastyou/__init__.py: DATA_PATH = PROJECT_PATH / ".data"
 _OUT_HW = {"acdc": (224, 224), "prostate": (224, 224)}  # the crops of semi_seg/augment.py
+# the ``transforms.Resize`` every transform of the data set begins with (ProstateStrongTransforms pretrain / label / val,
+# semi_seg/augment.py:57,74,86): applied ONCE to the train and the `val`-mode store when ``create_dataset`` builds them
+# (a folder: ``from_folder(resize=)``; a registered factory's store: ``.resized()``)
+_RESIZE = {"prostate": 224}
 
 
 def set_data_root(path: str):
@@ -87,13 +91,16 @@ def create_dataset(name: str, total_freedom: bool = True):
         tra_set, test_set = _FACTORIES[name]("train"), _FACTORIES[name]("val")
     elif name in _FOLDERS:
         folder, cls = _FOLDERS[name]
+        how = {"resize": _RESIZE[name]} if name in _RESIZE else {}  # every PNG by itself, before the slices are stacked
         root = os.path.join(_DATA_ROOT[0], folder)
         if not os.path.isdir(os.path.join(root, "train", "img")):
             raise FileNotFoundError(f"{name}: no data under {root} (the reference downloads it; here: set_data_root(...) or "
                                     f"register_dataset({name!r}, factory))")
-        tra_set, test_set = cls.from_folder(os.path.join(root, "train")), cls.from_folder(os.path.join(root, "val"))
+        tra_set, test_set = cls.from_folder(os.path.join(root, "train"), **how), cls.from_folder(os.path.join(root, "val"), **how)
     else:
         raise KeyError(name)
+    if name in _RESIZE:  # (factory stores too; a store ``from_folder(resize=)`` built is marked and comes back as it is)
+        tra_set, test_set = tra_set.resized(_RESIZE[name]), test_set.resized(_RESIZE[name])
     assert set(tra_set.get_scan_list()) & set(test_set.get_scan_list()) == set()
     tra_set.total_freedom = total_freedom  # creator.py:31 (``tra_transform._total_freedom``)
     return tra_set, test_set
@@ -111,6 +118,7 @@ def extract_sub_dataset_based_on_scan_names(dataset: DeviceSliceStore, group_nam
                         dict(dataset._scan_info),
                         targets=dataset.targets.index_select(0, idx) if dataset.targets is not None else None)
     sub.total_freedom = getattr(dataset, "total_freedom", True)
+    sub.resized_to = getattr(dataset, "resized_to", None)
     assert set(sub.get_scan_list()) == wanted
     return sub
 
@@ -212,7 +220,8 @@ class UnlabeledDeviceLoader:
             self._it = iter(self._sampler)
         if self._views is None:
             name = "prostate_pretrain" if getattr(self.dataset, "data_name", "acdc") == "prostate" else "acdc_pretrain"
-            self._views = RecipeViews(self.dataset.images, name, self._out_hw)
+            self._views = RecipeViews(self.dataset.images, name, self._out_hw,
+                                      resized_to=getattr(self.dataset, "resized_to", None))
         idx = [next(self._it) for _ in range(self._batch_size)]
         img, img_tf = self._views(idx)
         metas = [self.dataset.meta(i) for i in idx]

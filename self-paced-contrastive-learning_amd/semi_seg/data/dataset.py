@@ -13,6 +13,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
+from .augment import resize_labels, resize_shorter_edge, resize_store
 from .rearr import ContrastDataset
 
 
@@ -40,6 +41,7 @@ class DeviceSliceStore(ContrastDataset):
     partition_num = 3
     group_re = r"patient\d+_\d+"
     data_name = "acdc"
+    resized_to = None  # the ``Resize(size)`` this store has been through (``resized``, ``from_folder(resize=)``)
 
     def __init__(self, images: torch.Tensor, filenames: Sequence[str], scan_info: Optional[Dict[str, int]] = None,
                  targets: Optional[torch.Tensor] = None):
@@ -86,14 +88,36 @@ class DeviceSliceStore(ContrastDataset):
         f = self._filenames[index]
         return f, self._get_partition(f), self._get_scan_name(f)
 
+    def resized(self, size: int):
+        """``transforms.Resize(size)`` of the whole store, once (the Prostate recipes begin with it, semi_seg/augment.py:57,74,86):
+        images BILINEAR (``resize_store``), label maps NEAREST (``resize_labels``) -> a new store of the same class, filenames
+        and scan info, marked ``resized_to = size`` so that no loader built on it (or on a split of it) resizes again.  ``self``
+        when that mark is already there.  A store whose slices already have the resized shape needs no device call."""
+        size = int(size)
+        if self.resized_to == size:
+            return self
+        out = type(self)(resize_store(self.images, size), self._filenames, dict(self._scan_info),
+                         targets=resize_labels(self.targets, size) if self.targets is not None else None)
+        out.resized_to = size
+        if hasattr(self, "total_freedom"):
+            out.total_freedom = self.total_freedom
+        return out
+
     @classmethod
-    def from_folder(cls, root: str, device="cuda", size: Optional[int] = None):
+    def from_folder(cls, root: str, device="cuda", size: Optional[int] = None, resize: Optional[int] = None):
         """PNG folder ``root/img/*.png`` (+ ``root/gt/*.png`` label maps of the same stems when present: the reference's layout,
         contrastyou/data/dataset/base.py:76-140 ``sub_folders``) -> store.  Slices are centre-padded / cropped to ONE size (the
         store is one tensor); grey levels are kept as k / 255, label maps as uint8 class codes.  ``<name>_info.npy`` (scan ->
-        number of slices) is read when it lies next to the folders (semi_seg/data/dataset.py:28-31)."""
+        number of slices) is read when it lies next to the folders (semi_seg/data/dataset.py:28-31).
+
+        ``resize``: ``transforms.Resize(resize)`` of every PNG BY ITSELF, as the reference's transform sees it, before the slices
+        are stacked (no padding to the folder's largest size first): one bilinear and one nearest launch per source shape; the
+        store is marked ``resized_to``.  Slices whose resized shapes differ (non-square sources) cannot share one tensor:
+        ``ValueError``."""
         from PIL import Image
         import numpy as np
+        if resize is not None and size is not None:
+            raise ValueError("from_folder: `size` (centre pad / crop) and `resize` (Resize of every slice) exclude each other")
         files = sorted(f for f in os.listdir(os.path.join(root, "img")) if f.lower().endswith(".png"))
         arrs = [np.asarray(Image.open(os.path.join(root, "img", f)).convert("L"), dtype=np.uint8) for f in files]
         gt_dir = os.path.join(root, "gt")
@@ -104,6 +128,36 @@ class DeviceSliceStore(ContrastDataset):
                 raise FileNotFoundError(f"label maps missing for {len(missing)} slices, e.g. {missing[0]}")
             gts = [np.asarray(Image.open(os.path.join(gt_dir, f)).convert("L"), dtype=np.uint8) for f in files]
             assert all(a.shape == g.shape for a, g in zip(arrs, gts)), "a slice and its label map differ in size"
+        info = None
+        for name in ("acdc_info.npy", "prostate_info.npy"):
+            p = os.path.join(root, name)
+            if os.path.exists(p):
+                info = np.load(p, allow_pickle=True).item()
+        if resize is not None:
+            groups = OrderedDict()  # source shape -> positions in `files`
+            for k, a in enumerate(arrs):
+                groups.setdefault(a.shape, []).append(k)
+            shapes = sorted({resize_shorter_edge(hw, int(resize)) for hw in groups})
+            if len(shapes) != 1:
+                raise ValueError(f"from_folder(resize={resize}): the resized slices differ in shape ({shapes}, from sources "
+                                 f"{sorted(groups)}): they cannot share one store")
+            order = torch.tensor([k for ks in groups.values() for k in ks]).argsort().to(device)
+            ims, tgs = [], []
+            for ks in groups.values():
+                one = cls(torch.from_numpy(np.stack([arrs[k] for k in ks])).float().div_(255.0).to(device),
+                          [files[k] for k in ks], {},
+                          targets=torch.from_numpy(np.stack([gts[k] for k in ks])).to(device) if gts is not None else None
+                          ).resized(resize)
+                ims.append(one.images)
+                tgs.append(one.targets)
+            if len(ims) == 1:
+                images, targets = ims[0], tgs[0]
+            else:  # back into the folder's (sorted) file order
+                images = torch.cat(ims).index_select(0, order)
+                targets = torch.cat(tgs).index_select(0, order) if gts is not None else None
+            store = cls(images, files, info, targets=targets)
+            store.resized_to = int(resize)
+            return store
         size = size or max(max(a.shape) for a in arrs)
 
         def centred(list_of_arrays, dtype):
@@ -117,11 +171,6 @@ class DeviceSliceStore(ContrastDataset):
             return out
         images = centred(arrs, torch.float32) / 255.0
         targets = centred(gts, torch.uint8) if gts is not None else None
-        info = None
-        for name in ("acdc_info.npy", "prostate_info.npy"):
-            p = os.path.join(root, name)
-            if os.path.exists(p):
-                info = np.load(p, allow_pickle=True).item()
         return cls(images.to(device), files, info, targets=targets.to(device) if targets is not None else None)
 
 

@@ -40,7 +40,7 @@ class ContrastiveDeviceLoader:
             self._views = PretrainViews(store.images, out_hw, **legacy_recipe)
         else:
             name = recipe or ("prostate_pretrain" if getattr(store, "data_name", "acdc") == "prostate" else "acdc_pretrain")
-            self._views = RecipeViews(store.images, name, out_hw)
+            self._views = RecipeViews(store.images, name, out_hw, resized_to=getattr(store, "resized_to", None))
         self._batch_sampler, self._sampler, self._batch_size = batch_sampler, sampler, batch_size
         self._it = None
 
@@ -83,9 +83,8 @@ class LabeledDeviceLoader:
         self.dataset, self._batch_size = store, int(batch_size)
         name = recipe or ("prostate_label" if getattr(store, "data_name", "acdc") == "prostate" else "acdc_label")
         rec = dict(RECIPES[name]) if isinstance(name, str) else dict(name)
-        if rec.get("resize"):
-            raise NotImplementedError("resize the store (images BILINEAR, label maps NEAREST) before building the loader")
-        self._views = RecipeViews(store.images, rec, out_hw, labels=store.targets)
+        # (a recipe with ``resize`` on a store not yet ``resized`` to it: RecipeViews resizes images BILINEAR, label maps NEAREST)
+        self._views = RecipeViews(store.images, rec, out_hw, labels=store.targets, resized_to=getattr(store, "resized_to", None))
         self._sampler = sampler if sampler is not None else InfiniteRandomSampler(store, shuffle=True)
         self._total_freedom = bool(total_freedom)
         self._it = None
