@@ -1405,6 +1405,10 @@ __global__ __launch_bounds__(256) void image_wgrad_final_kernel(const float* __r
   }
 }
 
+// ---- host layer.  A launching entry point validates its arguments, fills ONE call descriptor (BnFwdArgs / BnBwdArgs: named
+// fields -- everything a launcher's behaviour depends on is in them) and makes one call.  The backward launcher runs in three
+// steps along BwdSums: obtain the sums, finalize, apply.
+
 // enough workgroups to fill the chip several times over, never more than the positions need
 static int stream_grid(size_t positions, int PL, int unroll, int cap) {
   size_t g = (positions + (size_t)PL * unroll - 1) / ((size_t)PL * unroll);
@@ -1413,192 +1417,280 @@ static int stream_grid(size_t positions, int PL, int unroll, int cap) {
   return (int)g;
 }
 
-// Pixel strides (in elements) of the activation written by the forward / of the activation gradient read by the backward when
-// they are channel slices of a wider tensor (the `_strided` entry points set them around their call; 0 = dense, CS).
-static thread_local int tl_act_stride = 0, tl_dact_stride = 0;
-static thread_local const void* tl_up2_src = nullptr;  // spcl_bnrelu_backward_up2: the fine gradient; `dact` is then WRITTEN
-static thread_local bool tl_acc_fill = false;  // spcl_bnrelu_backward_fill_acc: this call's reduction pass fills the block
+// Workgroup cap of a streaming pass with an accumulator block: coefficients derived from it are derived in every workgroup's
+// prologue (fewer, longer-lived workgroups amortise it); sums ADDED to it make ~100 adds per address at <= 768 workgroups.
+static int acc_stream_wg() {
+  static const int wg = lab_env("SPCL_ACC_STREAM_WG", 768);
+  return wg;
+}
+
+// The one dtype dispatch: f(T{}) launches with T the element type that `dtype` names, then the launch check; any other dtype
+// is refused -- all in the entry point's name.
+template <typename F>
+static int launch_as(int dtype, const char* who, F&& f) {
+  SPCL_CHECK_ARG(dtype == SPCL_F32 || dtype == SPCL_BF16, "%s: dtype %d", who, dtype);
+  if (dtype == SPCL_F32) f(float{});
+  else f(bf16_t{});
+  SPCL_LAUNCH_CHECK(who);
+  return SPCL_OK;
+}
+constexpr std::true_type yes{};  // template booleans chosen at run time (the pooled kernels' launch sites)
+constexpr std::false_type no{};
+
+// One forward call: act = relu(scale y + shift), optionally its 2 x 2 max-pool and the window maximum's raw y.
+struct BnFwdArgs {
+  const void* y = nullptr;  // [N][H][W][CS]
+  int N = 0, H = 0, W = 0, CS = 0;
+  const float *scale = nullptr, *shift = nullptr;  // the coefficients: these arrays, or ...
+  BnAccFwd bn{};                                   // ... bn.acc != null: derived from the block in every workgroup's prologue
+  void* act = nullptr;                             // [N][H][W] pixels act_stride elements apart (may be null with pool)
+  int act_stride = 0;                              // 0 = dense (CS); more: act is a channel slice of a wider tensor
+  void *pool = nullptr, *ymax = nullptr;           // [N][H/2][W/2][CS]; ymax (with pool): the window maximum's raw y
+  hipStream_t st = nullptr;
+};
 
 template <typename T>
-static int bnrelu_fwd_launch(const void* y, int N, int H, int W, int CS, const float* scale, const float* shift,
-                             void* act, void* pool, hipStream_t st, const BnAccFwd* bnp = nullptr,
-                             void* ymax = nullptr /* with pool: the window maximum's raw y, laid out like pool */) {
+static void bnrelu_fwd_launch(const BnFwdArgs& a) {
   constexpr int EPC = Chunk<T>::EPC;
-  const BnAccFwd bn = bnp != nullptr ? *bnp : BnAccFwd{};
-  // (coefficients derived in every workgroup's prologue: fewer, longer-lived workgroups amortise it)
-  static const int acc_wg = lab_env("SPCL_ACC_STREAM_WG", 768);
-  const int STREAM_MAX_WG = bnp != nullptr ? acc_wg : spcl::STREAM_MAX_WG;
-  const int PL = 256 / (CS / EPC);
-  const int AS = tl_act_stride > 0 ? tl_act_stride : CS;
-  const double tb = (double)N * H * W * CS * sizeof(T);  // bytes of one full-resolution tensor
-  prof_cost(tb * (1.0 + (act != nullptr ? 1.0 : 0.0) + (pool != nullptr ? 0.25 : 0.0) + (ymax != nullptr ? 0.25 : 0.0)), 0.0);
-  if (pool != nullptr) {
-    const int rows = N * ((H + 1) / 2);
-    const dim3 grid(rows < STREAM_MAX_WG ? rows : STREAM_MAX_WG);
-    const bool fast = H % 2 == 0 && W % 2 == 0;
-    if (ymax != nullptr && fast && act == nullptr) {
-      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, true, true, false>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift,
-                  (T*)act, (T*)pool, AS, bn, (T*)ymax);
-    } else if (ymax != nullptr && fast) {
-      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, true, true, true>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift,
-                  (T*)act, (T*)pool, AS, bn, (T*)ymax);
-    } else if (ymax != nullptr && act == nullptr) {
-      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, false, true, false>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift,
-                  (T*)act, (T*)pool, AS, bn, (T*)ymax);
-    } else if (ymax != nullptr) {
-      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, false, true, true>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift,
-                  (T*)act, (T*)pool, AS, bn, (T*)ymax);
-    } else if (fast) {
-      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, true>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift, (T*)act,
-                  (T*)pool, AS, bn, (T*)nullptr);
-    } else {
-      SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, false>), grid, dim3(256), 0, st, (const T*)y, N, H, W, CS, scale, shift, (T*)act,
-                  (T*)pool, AS, bn, (T*)nullptr);
-    }
-  } else {
-    const size_t npix = (size_t)N * H * W;
-    SPCL_LAUNCH((bnrelu_fwd_lin_kernel<T>), dim3(stream_grid(npix, PL, STREAM_UNROLL, STREAM_MAX_WG)), dim3(256), 0, st,
-                       (const T*)y, npix, CS, scale, shift, (T*)act, AS, bn);
+  const int max_wg = a.bn.acc != nullptr ? acc_stream_wg() : STREAM_MAX_WG;
+  const int AS = a.act_stride > 0 ? a.act_stride : a.CS;
+  const double tb = (double)a.N * a.H * a.W * a.CS * sizeof(T);  // bytes of one full-resolution tensor
+  prof_cost(tb * (1.0 + (a.act != nullptr ? 1.0 : 0.0) + (a.pool != nullptr ? 0.25 : 0.0) + (a.ymax != nullptr ? 0.25 : 0.0)), 0.0);
+  if (a.pool == nullptr) {
+    const size_t npix = (size_t)a.N * a.H * a.W;
+    SPCL_LAUNCH((bnrelu_fwd_lin_kernel<T>), dim3(stream_grid(npix, 256 / (a.CS / EPC), STREAM_UNROLL, max_wg)), dim3(256), 0,
+                a.st, (const T*)a.y, npix, a.CS, a.scale, a.shift, (T*)a.act, AS, a.bn);
+    return;
   }
-  return 0;
+  const int rows = a.N * ((a.H + 1) / 2);
+  const dim3 grid(rows < max_wg ? rows : max_wg);
+  auto go = [&](auto FAST, auto YMAX, auto ACT) {
+    SPCL_LAUNCH((bnrelu_fwd_pool_kernel<T, decltype(FAST)::value, decltype(YMAX)::value, decltype(ACT)::value>), grid, dim3(256),
+                0, a.st, (const T*)a.y, a.N, a.H, a.W, a.CS, a.scale, a.shift, (T*)a.act, (T*)a.pool, AS, a.bn, (T*)a.ymax);
+  };
+  const bool fast = a.H % 2 == 0 && a.W % 2 == 0;
+  if (a.ymax == nullptr) fast ? go(yes, no, yes) : go(no, no, yes);  // (ACT only tells the ymax forms apart)
+  else if (a.act == nullptr) fast ? go(yes, yes, no) : go(no, yes, no);
+  else fast ? go(yes, yes, yes) : go(no, yes, yes);
+}
+
+// The backward workspace's carve-up, in floats: the partial rows of up to BWD_MAX_WG workgroups ([nwg][sub-rows][CS]: 2
+// sub-rows, 11 on the image3 path), the folded coefficients [2][CS], then what only one path uses -- the image-wgrad pass
+// its partial taps [IMG_WGRAD_WG][9][CS] and a row [W] of zeros, image3 the folded autocorrelation rows [ACORR_FOLD][64].
+enum class BwdWs { Plain, ImageWgrad, Image3 };
+struct BwdWsLayout {
+  size_t partial = 0, ab, wpart, zrow, afold, total;
+  BwdWsLayout(BwdWs kind, int CS, int W = 0) {
+    ab = (size_t)BWD_MAX_WG * (kind == BwdWs::Image3 ? 11 : 2) * CS;
+    wpart = afold = ab + 2 * (size_t)CS;
+    zrow = wpart + (size_t)IMG_WGRAD_WG * 9 * CS;
+    total = kind == BwdWs::ImageWgrad ? zrow + (size_t)W : kind == BwdWs::Image3 ? afold + ACORR_FOLD * 64 : wpart;
+  }
+  size_t bytes() const { return total * sizeof(float); }
+};
+
+// One backward call says how the gradient arrives -- Full: dact, one value per pixel and channel; Pooled: dpool, behind the
+// 2 x 2 max-pool; PooledFull: dpool + dact (the activation is also consumed directly: skip connection, hook tap); PerImage:
+// dact [N][CS], one value per image and channel (behind a global average pool); Up2: d_up [N][2H][2W][CS], behind a x2
+// upsample, dact then being scratch the reduction pass WRITES the 2 x 2 sums to --
+enum class BnGrad { Full, Pooled, PooledFull, PerImage, Up2 };
+// where the sums (sum dz, sum dz yhat) come from -- Reduce: this call's reduction pass leaves partial rows in the workspace;
+// Rows: handed in per tile, second sum centred (the dgrad that produced the gradient left them); Filled: the accumulator block
+// is complete (that dgrad filled it); Fill: this call's reduction pass adds them to the (zeroed) block --
+enum class BnSums { Reduce, Rows, Filled, Fill };
+// and what the apply pass produces: dy, or (first conv of a one-channel image block) that conv's weight gradient dw, dy
+// being consumed in registers.
+enum class BnOut { Dy, ImageWgrad };
+struct BnBwdArgs {
+  const void* y = nullptr;  // [N][H][W][CS]
+  int N = 0, H = 0, W = 0, C = 0, CS = 0;
+  BnGrad grad = BnGrad::Full;
+  const void *dact = nullptr, *dpool = nullptr, *d_up = nullptr;
+  int dact_stride = 0;  // elements between two pixels of dact; 0 = dense (CS), more: a channel slice of a wider tensor
+  BnSums sums = BnSums::Reduce;
+  const float* rows = nullptr;  // Rows: [nrows][2][CS]
+  int nrows = 0, training = 0;
+  // the sums as a fixed-point block (bn_acc.hpp): Filled, Fill, or Rows that one launch adds to it -- no finalize launch, the
+  // apply kernel derives A, B in its prologue and its first workgroup writes dgamma / dbeta.  Null: through the workspace.
+  long long* acc = nullptr;
+  float* ws = nullptr;  // BwdWsLayout (may be null with a block: it is not touched then)
+  const float *mean = nullptr, *invstd = nullptr, *scale = nullptr, *shift = nullptr;
+  float *dgamma = nullptr, *dbeta = nullptr;
+  BnOut out = BnOut::Dy;
+  void* dy = nullptr;
+  const float* img = nullptr;  // ImageWgrad: the image [N][H][W] ...
+  float* dw = nullptr;         // ... and the weight gradient [C][1][3][3]
+  hipStream_t st = nullptr;
+
+  static BnGrad arrives(const void* dact, const void* dpool) {
+    return dpool == nullptr ? BnGrad::Full : dact == nullptr ? BnGrad::Pooled : BnGrad::PooledFull;
+  }
+  bool pooled() const { return grad == BnGrad::Pooled || grad == BnGrad::PooledFull; }
+  // the pooled kernels' whole-window form: even H, W and nothing but dpool (it takes no pixel stride)
+  bool whole_windows() const { return grad == BnGrad::Pooled && H % 2 == 0 && W % 2 == 0; }
+  size_t npix() const { return (size_t)N * H * W; }
+  int prows() const { return N * ((H + 1) / 2); }
+  int gstride() const { return dact_stride > 0 ? dact_stride : CS; }
+  int stream_wg() const { return acc != nullptr ? acc_stream_wg() : STREAM_MAX_WG; }
+  double grad_tensors() const { return (grad != BnGrad::Pooled ? 1.0 : 0.0) + (pooled() ? 0.25 : 0.0); }  // (its size, for prof_cost)
+  BnAccBwd block() const {
+    if (acc == nullptr) return BnAccBwd{};
+    return BnAccBwd{acc, mean /* = st[0]: mean, invstd, scale, shift are [4][CS] */, dgamma, dbeta, (float)npix(), training, C, CS};
+  }
+};
+
+// what the sums step leaves for the finalize launch and the apply pass
+struct BwdSums {
+  const float* fin_src = nullptr;     // the rows the finalize launch reduces ...
+  int nwg = 0, fin_transposed = 0;    // ... how many, and whether they are laid out [sub-row][channel][row]
+  int bsplit = 1;                     // PerImage: pixel splits per image (both passes)
+};
+
+// the pooled kernel's one launch site: reduction pass (APPLY false; `bw` = the block it fills at run time, if any) or apply pass
+// (the form that derives from a block is an instantiation of its own, see the kernel)
+template <typename T, bool APPLY>
+static void bnrelu_bwd_pool_launch(const BnBwdArgs& a, int grid, const float* ab, float* partial, const BnAccBwd& bw) {
+  const bool fast = a.whole_windows();
+  auto go = [&](auto FAST, auto ACC) {
+    SPCL_LAUNCH((bnrelu_bwd_pool_kernel<T, APPLY, decltype(FAST)::value, decltype(ACC)::value>), dim3(grid), dim3(256), 0, a.st,
+                (const T*)a.y, (const T*)a.dact, (const T*)a.dpool, a.N, a.H, a.W, a.CS, a.mean, a.invstd, a.scale, a.shift, ab,
+                partial, APPLY ? (T*)a.dy : (T*)nullptr, fast ? 0 : a.gstride(), bw);
+  };
+  if constexpr (APPLY) {
+    if (bw.acc != nullptr) return fast ? go(yes, yes) : go(no, yes);
+  }
+  fast ? go(yes, no) : go(no, no);
 }
 
 template <typename T>
-static int bnrelu_bwd_launch(const void* y, const void* dact, const void* dpool, int N, int H, int W, int C, int CS,
-                             const float* mean, const float* invstd, const float* scale, const float* shift,
-                             int training, float* ws, float* dgamma, float* dbeta, void* dy, hipStream_t st,
-                             const float* img = nullptr, float* dw = nullptr, const float* rows = nullptr,
-                             int nrows = 0, bool bcast = false /* dact is [N][CS], one value per image and channel */,
-                             long long* acc = nullptr /* the sums as a fixed-point block (bn_acc.hpp): no finalize launch */) {
-  constexpr int EPC = Chunk<T>::EPC;
-  // acc: either FILLED already by the dgrad that produced dact / dpool (lin / pool apply), or -- bcast -- filled by this
-  // call's reduction pass; the apply kernel derives A, B in its prologue, its first workgroup writes dgamma / dbeta
-  const BnAccBwd bw = acc != nullptr ? BnAccBwd{acc, mean /* = st[0]: mean, invstd, scale, shift are [4][CS] */, dgamma, dbeta,
-                                                (float)((size_t)N * H * W), training, C, CS}
-                                     : BnAccBwd{};
-  static const int acc_wg = lab_env("SPCL_ACC_STREAM_WG", 768);
-  const int STREAM_MAX_WG = acc != nullptr ? acc_wg : spcl::STREAM_MAX_WG;  // (see bnrelu_fwd_launch)
-  const bool pool = dpool != nullptr;
-  const bool fill = acc != nullptr && tl_acc_fill;  // the reduction pass below ADDS to the block (<= 768 workgroups: ~100 adds per address)
-  const int RED_MAX_WG = fill ? STREAM_MAX_WG : BWD_MAX_WG;
-  const int GS = tl_dact_stride > 0 ? tl_dact_stride : CS;
+static BwdSums bnrelu_bwd_sums(const BnBwdArgs& a, float* partial) {
   constexpr int rs = 2;  // sub-rows of a partial row (the image3 path has eleven: spcl_bnrelu_backward_rows_image3)
-  const Image3Args im3{nullptr, 0, nullptr, nullptr};
-  spcl_wgrad_tail* tail = img != nullptr ? take_tail_capture() : nullptr;
-  const int PL = 256 / (CS / EPC);
-  const size_t npix = (size_t)N * H * W;
-  const int prows = N * ((H + 1) / 2);
-  float* partial = ws;                           // [nwg][2][CS]  (ws may be null with `acc`: neither is touched then)
-  float* ab = ws != nullptr ? ws + (size_t)BWD_MAX_WG * 2 * CS : nullptr;  // [2][CS]: folded BN-backward coefficients
-  const float M = (float)npix;
-  int nwg, bsplit = 1;
-  const double tb = (double)npix * CS * sizeof(T);  // bytes of one full-resolution tensor
-  const double gb = (dact != nullptr ? tb : 0.0) + (pool ? 0.25 * tb : 0.0);
-  prof_cost(tb + gb, 0.0);
-  const float* fin_src = partial;
-  int fin_transposed = 0;
-  if (acc != nullptr && !bcast && !fill) {
-    nwg = 0;  // (the block is complete: nothing to reduce, nothing to finalize)
-  } else if (rows != nullptr && fill) {  // ... and go into the block: <= 512 workgroups add, the apply pass derives
-    const int G = (nrows + 511) / 512;
-    nwg = (nrows + G - 1) / G;
-    SPCL_LAUNCH(bwd_rows_acc_kernel, dim3(nwg), dim3(256), 0, st, rows, nrows, G, CS, acc);
-  } else if (rows != nullptr) {  // the partial sums came with the dgrad that produced dact (per conv tile, centred s2)
+  const int PL = 256 / (a.CS / Chunk<T>::EPC);
+  const double tb = (double)a.npix() * a.CS * sizeof(T);  // bytes of one full-resolution tensor
+  BwdSums s{partial};
+  prof_cost(tb + tb * a.grad_tensors(), 0.0);
+  if (a.sums == BnSums::Filled) return s;  // (the block is complete: nothing to reduce, nothing to finalize)
+  if (a.sums == BnSums::Rows) {
     static const int fin_rows = lab_env("SPCL_BWD_FIN_MAX_ROWS", BWD_MAX_WG);
-    if (nrows <= fin_rows) {
-      fin_src = rows;
-      nwg = nrows;
+    if (a.acc != nullptr) {  // ... go into the block: <= 512 workgroups add, the apply pass derives
+      const int G = (a.nrows + 511) / 512;
+      s.nwg = (a.nrows + G - 1) / G;
+      SPCL_LAUNCH(bwd_rows_acc_kernel, dim3(s.nwg), dim3(256), 0, a.st, a.rows, a.nrows, G, a.CS, a.acc);
+    } else if (a.nrows <= fin_rows) {  // the finalize launch reads them where they are
+      s.fin_src = a.rows;
+      s.nwg = a.nrows;
     } else {
-      const int G = (nrows + BWD_MAX_WG - 1) / BWD_MAX_WG;
-      nwg = (nrows + G - 1) / G;
+      const int G = (a.nrows + BWD_MAX_WG - 1) / BWD_MAX_WG;
+      s.nwg = (a.nrows + G - 1) / G;
       // (folded rows written transposed, [sub-row][channel][row]: the final kernel's loads are then coalesced)
-      SPCL_LAUNCH(bwd_rows_group_kernel, dim3(nwg), dim3(256), 0, st, rows, nrows, G, CS, partial, rs, nwg,
+      SPCL_LAUNCH(bwd_rows_group_kernel, dim3(s.nwg), dim3(256), 0, a.st, a.rows, a.nrows, G, a.CS, partial, rs, s.nwg,
                   (const float*)nullptr, 0, (float*)nullptr, 1);
-      fin_transposed = 1;
+      s.fin_transposed = 1;
     }
-  } else if (pool) {
-    nwg = prows < RED_MAX_WG ? prows : RED_MAX_WG;
-    const BnAccBwd rbw = fill ? bw : BnAccBwd{};
-    if (H % 2 == 0 && W % 2 == 0 && dact == nullptr && dpool != nullptr) {
-      SPCL_LAUNCH((bnrelu_bwd_pool_kernel<T, false, true>), dim3(nwg), dim3(256), 0, st, (const T*)y, (const T*)dact,
-                       (const T*)dpool, N, H, W, CS, mean, invstd, scale, shift, (const float*)nullptr, partial,
-                       (T*)nullptr, 0, rbw);
-    } else {
-      SPCL_LAUNCH((bnrelu_bwd_pool_kernel<T, false, false>), dim3(nwg), dim3(256), 0, st, (const T*)y, (const T*)dact,
-                       (const T*)dpool, N, H, W, CS, mean, invstd, scale, shift, (const float*)nullptr, partial,
-                       (T*)nullptr, GS, rbw);
-    }
-  } else if (bcast) {
-    // pixel splits per image: every workgroup leaves a row of 2 CS partial sums that bnrelu_bwd_fin_kernel walks one cache
-    // line per lane -- one pass of 8 pixels per workgroup (25 splits of a 14 x 14 map: 1 600 rows) made that kernel 9.5 us
-    // of the step; SPCL_BCAST_SPLIT_MAX splits -> N x that many rows
-    static const int env_split = lab_env("SPCL_BCAST_SPLIT_MAX", 4);
-    bsplit = (H * W + PL - 1) / PL;
-    if (env_split > 0 && bsplit > env_split) bsplit = env_split;
-    while (bsplit > 1 && N * bsplit > BWD_MAX_WG) bsplit = (bsplit + 1) / 2;
-    nwg = N * bsplit;
-    prof_cost(tb, 0.0);
-    SPCL_LAUNCH((bnrelu_bwd_reduce_bcast_kernel<T>), dim3(nwg), dim3(256), 0, st, (const T*)y, (const T*)dact, H * W, CS,
-                bsplit, mean, invstd, scale, shift, partial, acc);
-  } else if (tl_up2_src != nullptr) {
-    nwg = stream_grid(npix, PL, STREAM_UNROLL, RED_MAX_WG);
-    prof_cost(tb * 6.0, 0.0);
-    SPCL_LAUNCH((bnrelu_bwd_reduce_up2_kernel<T>), dim3(nwg), dim3(256), 0, st, (const T*)y, (const T*)tl_up2_src, (T*)dact,
-                npix, W, CS, mean, invstd, scale, shift, partial, fill ? acc : (long long*)nullptr);
-  } else {
-    nwg = stream_grid(npix, PL, STREAM_UNROLL, RED_MAX_WG);
-    SPCL_LAUNCH((bnrelu_bwd_reduce_lin_kernel<T>), dim3(nwg), dim3(256), 0, st, (const T*)y, (const T*)dact, npix,
-                       CS, mean, invstd, scale, shift, partial, GS, fill ? acc : (long long*)nullptr);
+    return s;
   }
-  float* zrow = ab != nullptr ? ab + 2 * CS + (size_t)IMG_WGRAD_WG * 9 * CS : nullptr;  // [W] zeros (image-wgrad pass only, see below)
-  if (acc == nullptr)
-    SPCL_LAUNCH(bnrelu_bwd_fin_kernel, dim3(CS), dim3(256), 0, st, fin_src, nwg, C, CS,
-                       M, training, mean, invstd, scale, dgamma, dbeta, ab, img != nullptr ? zrow : (float*)nullptr,
-                       img != nullptr ? W : 0, rows != nullptr ? 1 : 0, rs, im3, fin_transposed);
-  prof_cost(2.0 * tb + gb, 0.0);
-  if (pool) {
-    if (H % 2 == 0 && W % 2 == 0 && dact == nullptr && dpool != nullptr) {
-      if (acc != nullptr)
-        SPCL_LAUNCH((bnrelu_bwd_pool_kernel<T, true, true, true>), dim3(prows < STREAM_MAX_WG ? prows : STREAM_MAX_WG), dim3(256), 0, st,
-                    (const T*)y, (const T*)dact, (const T*)dpool, N, H, W, CS, mean, invstd, scale, shift, (const float*)ab,
-                    (float*)nullptr, (T*)dy, 0, bw);
-      else
-        SPCL_LAUNCH((bnrelu_bwd_pool_kernel<T, true, true>), dim3(prows < STREAM_MAX_WG ? prows : STREAM_MAX_WG), dim3(256), 0, st, (const T*)y,
-                       (const T*)dact, (const T*)dpool, N, H, W, CS, mean, invstd, scale, shift, (const float*)ab,
-                       (float*)nullptr, (T*)dy);
-    } else {
-      if (acc != nullptr)
-        SPCL_LAUNCH((bnrelu_bwd_pool_kernel<T, true, false, true>), dim3(prows < STREAM_MAX_WG ? prows : STREAM_MAX_WG), dim3(256), 0, st,
-                    (const T*)y, (const T*)dact, (const T*)dpool, N, H, W, CS, mean, invstd, scale, shift, (const float*)ab,
-                    (float*)nullptr, (T*)dy, GS, bw);
-      else
-        SPCL_LAUNCH((bnrelu_bwd_pool_kernel<T, true, false>), dim3(prows < STREAM_MAX_WG ? prows : STREAM_MAX_WG), dim3(256), 0, st, (const T*)y,
-                       (const T*)dact, (const T*)dpool, N, H, W, CS, mean, invstd, scale, shift, (const float*)ab,
-                       (float*)nullptr, (T*)dy, GS);
+  // this call reduces: rows of partial sums, or -- Fill -- adds to the block
+  long long* const fill = a.sums == BnSums::Fill ? a.acc : nullptr;
+  const int red_wg = fill != nullptr ? a.stream_wg() : BWD_MAX_WG;
+  switch (a.grad) {
+    case BnGrad::Pooled:
+    case BnGrad::PooledFull:
+      s.nwg = a.prows() < red_wg ? a.prows() : red_wg;
+      bnrelu_bwd_pool_launch<T, false>(a, s.nwg, nullptr, partial, fill != nullptr ? a.block() : BnAccBwd{});
+      break;
+    case BnGrad::PerImage: {
+      // pixel splits per image: every workgroup leaves a row of 2 CS partial sums that bnrelu_bwd_fin_kernel walks one cache
+      // line per lane -- one pass of 8 pixels per workgroup (25 splits of a 14 x 14 map: 1 600 rows) made that kernel 9.5 us
+      // of the step; SPCL_BCAST_SPLIT_MAX splits -> N x that many rows
+      static const int env_split = lab_env("SPCL_BCAST_SPLIT_MAX", 4);
+      s.bsplit = (a.H * a.W + PL - 1) / PL;
+      if (env_split > 0 && s.bsplit > env_split) s.bsplit = env_split;
+      while (s.bsplit > 1 && a.N * s.bsplit > BWD_MAX_WG) s.bsplit = (s.bsplit + 1) / 2;
+      s.nwg = a.N * s.bsplit;
+      prof_cost(tb, 0.0);
+      SPCL_LAUNCH((bnrelu_bwd_reduce_bcast_kernel<T>), dim3(s.nwg), dim3(256), 0, a.st, (const T*)a.y, (const T*)a.dact,
+                  a.H * a.W, a.CS, s.bsplit, a.mean, a.invstd, a.scale, a.shift, partial, fill);
+      break;
     }
-  } else if (img != nullptr) {  // first conv of a one-channel image block: dy is consumed in registers by its dW
-    float* wpart = ab + 2 * CS;  // [IMG_WGRAD_WG][9][CS];  zrow = the image row above / below the image
+    case BnGrad::Up2:
+      s.nwg = stream_grid(a.npix(), PL, STREAM_UNROLL, red_wg);
+      prof_cost(tb * 6.0, 0.0);
+      SPCL_LAUNCH((bnrelu_bwd_reduce_up2_kernel<T>), dim3(s.nwg), dim3(256), 0, a.st, (const T*)a.y, (const T*)a.d_up,
+                  (T*)a.dact, a.npix(), a.W, a.CS, a.mean, a.invstd, a.scale, a.shift, partial, fill);
+      break;
+    case BnGrad::Full:
+      s.nwg = stream_grid(a.npix(), PL, STREAM_UNROLL, red_wg);
+      SPCL_LAUNCH((bnrelu_bwd_reduce_lin_kernel<T>), dim3(s.nwg), dim3(256), 0, a.st, (const T*)a.y, (const T*)a.dact, a.npix(),
+                  a.CS, a.mean, a.invstd, a.scale, a.shift, partial, a.gstride(), fill);
+      break;
+  }
+  return s;
+}
+
+// rows -> dgamma, dbeta and the folded coefficients `ab` (with a block there is nothing to do: the apply pass derives)
+static void bnrelu_bwd_finalize(const BnBwdArgs& a, const BwdSums& s, float* ab, float* zrow) {
+  if (a.acc != nullptr) return;
+  const bool image = a.out == BnOut::ImageWgrad;  // its apply pass reads a row of zeros above / below the image
+  SPCL_LAUNCH(bnrelu_bwd_fin_kernel, dim3(a.CS), dim3(256), 0, a.st, s.fin_src, s.nwg, a.C, a.CS, (float)a.npix(), a.training,
+              a.mean, a.invstd, a.scale, a.dgamma, a.dbeta, ab, image ? zrow : (float*)nullptr, image ? a.W : 0,
+              a.sums == BnSums::Rows ? 1 : 0, 2, Image3Args{nullptr, 0, nullptr, nullptr}, s.fin_transposed);
+}
+
+template <typename T>
+static void bnrelu_bwd_apply(const BnBwdArgs& a, const BwdSums& s, const float* ab, float* wpart, const float* zrow) {
+  const int PL = 256 / (a.CS / Chunk<T>::EPC);
+  const double tb = (double)a.npix() * a.CS * sizeof(T);  // bytes of one full-resolution tensor
+  const BnAccBwd bw = a.block();
+  prof_cost(2.0 * tb + tb * a.grad_tensors(), 0.0);
+  if (a.out == BnOut::ImageWgrad) {  // wpart [IMG_WGRAD_WG][9][CS];  zrow = the image row above / below the image
+    spcl_wgrad_tail* tail = take_tail_capture();
     static const int want = lab_env("SPCL_IMGWG_WG", 1280);  // 5 resident per CU
     const int cap = want < IMG_WGRAD_WG ? (want > 0 ? want : 1) : IMG_WGRAD_WG;
-    const int g = N * H < cap ? N * H : cap;
-    prof_cost(2.0 * tb + (double)npix * 4, 2.0 * 9 * npix * C);
-    SPCL_LAUNCH((bnrelu_bwd_image_wgrad_kernel<T>), dim3(g), dim3(256), 4 * 9 * CS * sizeof(float), st, (const T*)y,
-                       (const T*)dact, img, N, H, W, CS, scale, shift, (const float*)ab, (const float*)zrow, wpart);
+    const int g = a.N * a.H < cap ? a.N * a.H : cap;
+    prof_cost(2.0 * tb + (double)a.npix() * 4, 2.0 * 9 * a.npix() * a.C);
+    SPCL_LAUNCH((bnrelu_bwd_image_wgrad_kernel<T>), dim3(g), dim3(256), 4 * 9 * a.CS * sizeof(float), a.st, (const T*)a.y,
+                (const T*)a.dact, a.img, a.N, a.H, a.W, a.CS, a.scale, a.shift, ab, zrow, wpart);
     if (tail != nullptr) {  // the nine taps' final sums ride in the batched weight-gradient reduction
-      tail->partial = wpart; tail->dw = dw; tail->kind = 1; tail->nsplit = g; tail->nblk_ci = tail->nblk_co = 1;
-      tail->CIB = 1; tail->COB = CS; tail->Cin = 1; tail->Cout = C;
+      tail->partial = wpart; tail->dw = a.dw; tail->kind = 1; tail->nsplit = g; tail->nblk_ci = tail->nblk_co = 1;
+      tail->CIB = 1; tail->COB = a.CS; tail->Cin = 1; tail->Cout = a.C;
     } else {
-      SPCL_LAUNCH(image_wgrad_final_kernel, dim3(9), dim3(256), 0, st, (const float*)wpart, g, C, CS, dw);
+      SPCL_LAUNCH(image_wgrad_final_kernel, dim3(9), dim3(256), 0, a.st, (const float*)wpart, g, a.C, a.CS, a.dw);
     }
-  } else if (bcast) {
+  } else if (a.pooled()) {
+    bnrelu_bwd_pool_launch<T, true>(a, a.prows() < a.stream_wg() ? a.prows() : a.stream_wg(), ab, nullptr, bw);
+  } else if (a.grad == BnGrad::PerImage) {
     prof_cost(2.0 * tb, 0.0);
-    SPCL_LAUNCH((bnrelu_bwd_apply_bcast_kernel<T>), dim3(N * bsplit), dim3(256), 0, st, (const T*)y, (const T*)dact, H * W,
-                CS, bsplit, scale, shift, (const float*)ab, (T*)dy, bw);
-  } else {
-    SPCL_LAUNCH((bnrelu_bwd_apply_lin_kernel<T>), dim3(stream_grid(npix, PL, STREAM_UNROLL, STREAM_MAX_WG)), dim3(256), 0,
-                       st, (const T*)y, (const T*)dact, npix, CS, scale, shift, (const float*)ab, (T*)dy, GS, bw);
+    SPCL_LAUNCH((bnrelu_bwd_apply_bcast_kernel<T>), dim3(a.N * s.bsplit), dim3(256), 0, a.st, (const T*)a.y, (const T*)a.dact,
+                a.H * a.W, a.CS, s.bsplit, a.scale, a.shift, ab, (T*)a.dy, bw);
+  } else {  // Full, Up2 (whose reduction pass left the 2 x 2 sums in dact)
+    SPCL_LAUNCH((bnrelu_bwd_apply_lin_kernel<T>), dim3(stream_grid(a.npix(), PL, STREAM_UNROLL, a.stream_wg())), dim3(256), 0,
+                a.st, (const T*)a.y, (const T*)a.dact, a.npix(), a.CS, a.scale, a.shift, ab, (T*)a.dy, a.gstride(), bw);
   }
-  return 0;
+}
+
+template <typename T>
+static void bnrelu_bwd_launch(const BnBwdArgs& a) {
+  const BwdWsLayout l(a.out == BnOut::ImageWgrad ? BwdWs::ImageWgrad : BwdWs::Plain, a.CS, a.W);
+  auto at = [&](size_t off) { return a.ws != nullptr ? a.ws + off : nullptr; };
+  const BwdSums s = bnrelu_bwd_sums<T>(a, at(l.partial));
+  bnrelu_bwd_finalize(a, s, at(l.ab), at(l.zrow));
+  bnrelu_bwd_apply<T>(a, s, at(l.ab), at(l.wpart), at(l.zrow));
+}
+
+// validates a spcl_bn_acc against the call's CS and builds the kernels' view of it
+static int bn_acc_fwd(const char* who, const spcl_bn_acc* bn, int CS, BnAccFwd* out) {
+  SPCL_CHECK_ARG(bn->acc && bn->gamma && bn->beta && bn->st && bn->CS == CS && bn->C > 0 && bn->C <= CS && bn->count >= 1.f,
+                 "%s: bad accumulator description", who);
+  *out = BnAccFwd{bn->acc, bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->num_batches_tracked, bn->st,
+                  bn->momentum, bn->eps, bn->count, bn->C, bn->CS, 1.0 / (double)bn->count};
+  return SPCL_OK;
+}
+
+static int bnrelu_fwd_run(const char* who, int dtype, const BnFwdArgs& a) {
+  return launch_as(dtype, who, [&](auto t) { bnrelu_fwd_launch<decltype(t)>(a); });
+}
+static int bnrelu_bwd_run(const char* who, int dtype, const BnBwdArgs& a) {
+  return launch_as(dtype, who, [&](auto t) { bnrelu_bwd_launch<decltype(t)>(a); });
 }
 
 }  // namespace spcl
@@ -1706,20 +1798,35 @@ extern "C" int spcl_bn_eval_affine_multi(const spcl_bn_eval_item* items, int n, 
   return SPCL_OK;
 }
 
+// what spcl_bnrelu_pool_forward and its strided form share: their checks, then the launch
+static int pool_forward_run(const char* who, int dtype, const BnFwdArgs& a) {
+  SPCL_CHECK_ARG(a.y && a.scale && a.shift && (a.act || a.pool), "%s: null pointer", who);
+  SPCL_CHECK_ARG(a.N > 0 && a.H > 0 && a.W > 0 && a.CS > 0 && a.CS % 16 == 0 && a.CS <= 1024, "%s: bad shape", who);
+  SPCL_CHECK_ARG(!a.pool || (a.H >= 2 && a.W >= 2), "%s: 2x2 pooling needs H,W >= 2", who);
+  return bnrelu_fwd_run(who, dtype, a);
+}
+
+static BnFwdArgs fwd_args(const void* y, int N, int H, int W, int CS, const float* scale, const float* shift, void* act,
+                          void* pool, void* stream) {
+  BnFwdArgs a;
+  a.y = y; a.N = N; a.H = H; a.W = W; a.CS = CS; a.scale = scale; a.shift = shift; a.act = act; a.pool = pool;
+  a.st = (hipStream_t)stream;
+  return a;
+}
+
 extern "C" int spcl_bnrelu_pool_forward(const void* y, int dtype, int N, int H, int W, int CS, const float* scale,
                                         const float* shift, void* act_out, void* pool_out, void* stream) {
-  SPCL_CHECK_ARG(y && scale && shift && (act_out || pool_out), "bnrelu_pool_forward: null pointer");
-  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && CS > 0 && CS % 16 == 0 && CS <= 1024, "bnrelu_pool_forward: bad shape");
-  SPCL_CHECK_ARG(!pool_out || (H >= 2 && W >= 2), "bnrelu_pool_forward: 2x2 pooling needs H,W >= 2");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype != SPCL_F32 && dtype != SPCL_BF16) {
-    set_error("bnrelu_pool_forward: dtype %d", dtype);
-    return SPCL_EINVAL;
-  }
-  if (dtype == SPCL_F32) bnrelu_fwd_launch<float>(y, N, H, W, CS, scale, shift, act_out, pool_out, st);
-  else bnrelu_fwd_launch<bf16_t>(y, N, H, W, CS, scale, shift, act_out, pool_out, st);
-  SPCL_LAUNCH_CHECK("bnrelu_pool_forward");
-  return SPCL_OK;
+  const BnFwdArgs a = fwd_args(y, N, H, W, CS, scale, shift, act_out, pool_out, stream);
+  return pool_forward_run("bnrelu_pool_forward", dtype, a);
+}
+
+extern "C" int spcl_bnrelu_pool_forward_strided(const void* y, int dtype, int N, int H, int W, int CS, const float* scale,
+                                                const float* shift, void* act_out, int act_stride, void* pool_out, void* stream) {
+  SPCL_CHECK_ARG(act_out && act_stride >= CS && act_stride % 8 == 0,
+                 "bnrelu_pool_forward_strided: act_out with a pixel stride >= CS, a multiple of 8 elements");
+  BnFwdArgs a = fwd_args(y, N, H, W, CS, scale, shift, act_out, pool_out, stream);
+  a.act_stride = act_stride;
+  return pool_forward_run("bnrelu_pool_forward_strided", dtype, a);
 }
 
 // BN-apply + ReLU with the activation's global average per (image, channel) as a side output (bnrelu_fwd_gap_kernel): the
@@ -1731,27 +1838,19 @@ extern "C" int spcl_bnrelu_gap_supported(int dtype, int H, int W, int C, int CS)
 }
 
 extern "C" int spcl_bnrelu_gap_forward(const void* y, int dtype, int N, int H, int W, int C, int CS, const float* scale,
-                                       const float* shift, const spcl_bn_acc* bn, void* act_out, float* gap_out,
-                                       void* stream) {
+                                       const float* shift, const spcl_bn_acc* bn, void* act_out, float* gap_out, void* stream) {
   SPCL_CHECK_ARG(y && act_out && gap_out && (bn || (scale && shift)), "bnrelu_gap_forward: null pointer");
   SPCL_CHECK_ARG(N > 0 && spcl_bnrelu_gap_supported(dtype, H, W, C, CS), "bnrelu_gap_forward: unsupported shape / dtype");
   BnAccFwd f{};
-  if (bn != nullptr) {
-    SPCL_CHECK_ARG(bn->acc && bn->gamma && bn->beta && bn->st && bn->CS == CS && bn->C > 0 && bn->C <= CS && bn->count >= 1.f,
-                   "bnrelu_gap_forward: bad accumulator description");
-    f = BnAccFwd{bn->acc, bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->num_batches_tracked, bn->st,
-                 bn->momentum, bn->eps, bn->count, bn->C, bn->CS, 1.0 / (double)bn->count};
-  }
+  if (bn != nullptr)
+    if (const int rc = bn_acc_fwd("bnrelu_gap_forward", bn, CS, &f)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int CW = CS % 64 == 0 ? 64 : CS;  // channels per workgroup: 64-channel windows (128 bytes of a bf16 pixel) where they tile
-  if (dtype == SPCL_F32)
-    SPCL_LAUNCH((bnrelu_fwd_gap_kernel<float>), dim3(N, CS / CW), dim3(256), 0, st, (const float*)y, H * W, C, CS, CW, scale,
-                shift, (float*)act_out, gap_out, f);
-  else
-    SPCL_LAUNCH((bnrelu_fwd_gap_kernel<bf16_t>), dim3(N, CS / CW), dim3(256), 0, st, (const bf16_t*)y, H * W, C, CS, CW, scale,
-                shift, (bf16_t*)act_out, gap_out, f);
-  SPCL_LAUNCH_CHECK("bnrelu_gap_forward");
-  return SPCL_OK;
+  return launch_as(dtype, "bnrelu_gap_forward", [&](auto t) {
+    using T = decltype(t);
+    SPCL_LAUNCH((bnrelu_fwd_gap_kernel<T>), dim3(N, CS / CW), dim3(256), 0, st, (const T*)y, H * W, C, CS, CW, scale, shift,
+                (T*)act_out, gap_out, f);
+  });
 }
 
 // BN-apply + ReLU (+ 2x2 max-pool) with scale / shift DERIVED from a fixed-point accumulator block (bn_acc.hpp) in the kernel's
@@ -1762,19 +1861,9 @@ extern "C" int spcl_bnrelu_pool_forward_acc(const void* y, int dtype, int N, int
   SPCL_CHECK_ARG(y && bn && (act_out || pool_out), "bnrelu_pool_forward_acc: null pointer");
   SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && CS > 0 && CS % 16 == 0 && CS <= 256, "bnrelu_pool_forward_acc: bad shape (CS <= 256)");
   SPCL_CHECK_ARG(!pool_out || (H >= 2 && W >= 2), "bnrelu_pool_forward_acc: 2x2 pooling needs H,W >= 2");
-  SPCL_CHECK_ARG(bn->acc && bn->gamma && bn->beta && bn->st && bn->CS == CS && bn->C > 0 && bn->C <= CS && bn->count >= 1.f,
-                 "bnrelu_pool_forward_acc: bad accumulator description");
-  hipStream_t st = (hipStream_t)stream;
-  const BnAccFwd f{bn->acc, bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->num_batches_tracked, bn->st,
-                   bn->momentum, bn->eps, bn->count, bn->C, bn->CS, 1.0 / (double)bn->count};
-  if (dtype == SPCL_F32) bnrelu_fwd_launch<float>(y, N, H, W, CS, nullptr, nullptr, act_out, pool_out, st, &f);
-  else if (dtype == SPCL_BF16) bnrelu_fwd_launch<bf16_t>(y, N, H, W, CS, nullptr, nullptr, act_out, pool_out, st, &f);
-  else {
-    set_error("bnrelu_pool_forward_acc: dtype %d", dtype);
-    return SPCL_EINVAL;
-  }
-  SPCL_LAUNCH_CHECK("bnrelu_pool_forward_acc");
-  return SPCL_OK;
+  BnFwdArgs a = fwd_args(y, N, H, W, CS, nullptr, nullptr, act_out, pool_out, stream);
+  if (const int rc = bn_acc_fwd("bnrelu_pool_forward_acc", bn, CS, &a.bn)) return rc;
+  return bnrelu_fwd_run("bnrelu_pool_forward_acc", dtype, a);
 }
 
 // spcl_bnrelu_pool_forward / _acc with the window maximum's RAW y as a side output: ymax_out [N][H/2][W/2][CS], per complete
@@ -1787,49 +1876,11 @@ extern "C" int spcl_bnrelu_pool_forward_ymax(const void* y, int dtype, int N, in
   SPCL_CHECK_ARG(N > 0 && H >= 2 && W >= 2 && CS > 0 && CS % 16 == 0 && CS <= (bn ? 256 : 1024),
                  "bnrelu_pool_forward_ymax: bad shape (H, W >= 2; CS <= 256 with an accumulator block)");
   SPCL_CHECK_ARG(dtype == SPCL_F32 || dtype == SPCL_BF16, "bnrelu_pool_forward_ymax: dtype");
-  BnAccFwd f{};
-  if (bn != nullptr) {
-    SPCL_CHECK_ARG(bn->acc && bn->gamma && bn->beta && bn->st && bn->CS == CS && bn->C > 0 && bn->C <= CS && bn->count >= 1.f,
-                   "bnrelu_pool_forward_ymax: bad accumulator description");
-    f = BnAccFwd{bn->acc, bn->gamma, bn->beta, bn->running_mean, bn->running_var, bn->num_batches_tracked, bn->st,
-                 bn->momentum, bn->eps, bn->count, bn->C, bn->CS, 1.0 / (double)bn->count};
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SPCL_F32)
-    bnrelu_fwd_launch<float>(y, N, H, W, CS, scale, shift, act_out, pool_out, st, bn != nullptr ? &f : nullptr, ymax_out);
-  else
-    bnrelu_fwd_launch<bf16_t>(y, N, H, W, CS, scale, shift, act_out, pool_out, st, bn != nullptr ? &f : nullptr, ymax_out);
-  SPCL_LAUNCH_CHECK("bnrelu_pool_forward_ymax");
-  return SPCL_OK;
-}
-
-// BN + ReLU (+ max-pool) BACKWARD apply pass with its coefficients derived from a fixed-point accumulator block: no reduction
-// pass over the tensors where the dgrad that produced the incoming gradient filled the block (spcl_conv3x3_dgrad_bnstats_acc /
-// _poolstats_acc), and no finalize launch in any case.  Exactly one of
-//   dact    [N][H][W][CS]      gradient w.r.t. the activation; the block is already filled
-//   dpool   [N][H/2][W/2][CS]  gradient w.r.t. the pooled activation (H, W even); the block is already filled
-//   dact_nc [N][CS]            one value per (image, channel) (global average pool); THIS call's reduction pass fills the block
-// st = the forward's [4][CS] (mean, invstd, scale, shift).  The first workgroup of the apply launch writes dgamma / dbeta.
-extern "C" int spcl_bnrelu_backward_acc(const void* y, const void* dact, const void* dpool, const void* dact_nc, int dtype,
-                                        int N, int H, int W, int C, int CS, const float* st4, int training, long long* acc,
-                                        float* dgamma, float* dbeta, void* dy, void* stream) {
-  SPCL_CHECK_ARG(y && st4 && acc && dgamma && dbeta && dy, "bnrelu_backward_acc: null pointer");
-  SPCL_CHECK_ARG((dact != nullptr) + (dpool != nullptr) + (dact_nc != nullptr) == 1,
-                 "bnrelu_backward_acc: exactly one of dact, dpool, dact_nc");
-  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && CS >= C && CS % 16 == 0 && CS <= 256, "bnrelu_backward_acc: bad shape (CS <= 256)");
-  SPCL_CHECK_ARG(!dpool || (H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0), "bnrelu_backward_acc: pooled form needs even H, W");
-  SPCL_CHECK_ARG(dtype == SPCL_BF16 || dtype == SPCL_F32, "bnrelu_backward_acc: dtype %d", dtype);
-  hipStream_t st = (hipStream_t)stream;
-  const float *mean = st4, *invstd = st4 + CS, *scale = st4 + 2 * CS, *shift = st4 + 3 * CS;
-  const void* g = dact_nc != nullptr ? dact_nc : dact;
-  if (dtype == SPCL_F32)
-    bnrelu_bwd_launch<float>(y, g, dpool, N, H, W, C, CS, mean, invstd, scale, shift, training, nullptr, dgamma, dbeta, dy, st,
-                             nullptr, nullptr, nullptr, 0, dact_nc != nullptr, acc);
-  else
-    bnrelu_bwd_launch<bf16_t>(y, g, dpool, N, H, W, C, CS, mean, invstd, scale, shift, training, nullptr, dgamma, dbeta, dy, st,
-                              nullptr, nullptr, nullptr, 0, dact_nc != nullptr, acc);
-  SPCL_LAUNCH_CHECK("bnrelu_backward_acc");
-  return SPCL_OK;
+  BnFwdArgs a = fwd_args(y, N, H, W, CS, scale, shift, act_out, pool_out, stream);
+  a.ymax = ymax_out;
+  if (bn != nullptr)
+    if (const int rc = bn_acc_fwd("bnrelu_pool_forward_ymax", bn, CS, &a.bn)) return rc;
+  return bnrelu_fwd_run("bnrelu_pool_forward_ymax", dtype, a);
 }
 
 extern "C" int spcl_bnrelu_up2_forward(const void* y, int dtype, int N, int H, int W, int CS, const float* scale,
@@ -1841,88 +1892,94 @@ extern "C" int spcl_bnrelu_up2_forward(const void* y, int dtype, int N, int H, i
   const unsigned grid = nrows < (unsigned)STREAM_MAX_WG ? nrows : (unsigned)STREAM_MAX_WG;
   const double tb = (double)N * H * W * CS * (dtype == SPCL_F32 ? 4.0 : 2.0);
   prof_cost(5.0 * tb, 0.0);
-  if (dtype == SPCL_F32)
-    SPCL_LAUNCH((bnrelu_fwd_up2_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)y, nrows, W, CS, scale, shift,
-                (float*)up_out);
-  else if (dtype == SPCL_BF16)
-    SPCL_LAUNCH((bnrelu_fwd_up2_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)y, nrows, W, CS, scale, shift,
-                (bf16_t*)up_out);
-  else {
-    set_error("bnrelu_up2_forward: dtype %d", dtype);
-    return SPCL_EINVAL;
-  }
-  SPCL_LAUNCH_CHECK("bnrelu_up2_forward");
-  return SPCL_OK;
+  return launch_as(dtype, "bnrelu_up2_forward", [&](auto t) {
+    using T = decltype(t);
+    SPCL_LAUNCH((bnrelu_fwd_up2_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)y, nrows, W, CS, scale, shift, (T*)up_out);
+  });
 }
 
-extern "C" int spcl_bnrelu_pool_forward_strided(const void* y, int dtype, int N, int H, int W, int CS, const float* scale,
-                                                const float* shift, void* act_out, int act_stride, void* pool_out,
-                                                void* stream) {
-  SPCL_CHECK_ARG(act_out && act_stride >= CS && act_stride % 8 == 0,
-                 "bnrelu_pool_forward_strided: act_out with a pixel stride >= CS, a multiple of 8 elements");
-  tl_act_stride = act_stride;
-  const int rc = spcl_bnrelu_pool_forward(y, dtype, N, H, W, CS, scale, shift, act_out, pool_out, stream);
-  tl_act_stride = 0;
-  return rc;
+// The backward entry points.  Common to their descriptors: the tensors' shape, the forward's coefficients, where dgamma / dbeta
+// go, and the workspace ...
+static BnBwdArgs bwd_args(const void* y, int N, int H, int W, int C, int CS, const float* mean, const float* invstd,
+                          const float* scale, const float* shift, int training, float* ws, float* dgamma, float* dbeta,
+                          void* stream) {
+  BnBwdArgs a;
+  a.y = y; a.N = N; a.H = H; a.W = W; a.C = C; a.CS = CS; a.training = training; a.dgamma = dgamma; a.dbeta = dbeta;
+  a.mean = mean; a.invstd = invstd; a.scale = scale; a.shift = shift; a.ws = ws; a.st = (hipStream_t)stream;
+  return a;
+}
+// ... or the accumulator block, the coefficients then as st4 = the forward's [4][CS] (mean, invstd, scale, shift)
+static BnBwdArgs bwd_args(const void* y, int N, int H, int W, int C, int CS, const float* st4, int training, long long* acc,
+                          float* dgamma, float* dbeta, void* stream) {
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, st4, st4 + CS, st4 + 2 * CS, st4 + 3 * CS, training, nullptr, dgamma, dbeta, stream);
+  a.acc = acc;
+  return a;
 }
 
-extern "C" size_t spcl_bnrelu_bwd_workspace_bytes(int N, int H, int W, int CS) {
-  (void)N; (void)H; (void)W;
-  return ((size_t)BWD_MAX_WG * 2 * CS + 2 * (size_t)CS) * sizeof(float);
+// what spcl_bnrelu_pool_backward, its strided form and spcl_bnrelu_backward_up2 share: their checks, then the launch
+static int pool_backward_run(const char* who, int dtype, const BnBwdArgs& a) {
+  SPCL_CHECK_ARG(a.y && (a.dact || a.dpool) && a.mean && a.invstd && a.scale && a.shift && a.ws && a.dgamma && a.dbeta && a.dy,
+                 "%s: null pointer", who);
+  SPCL_CHECK_ARG(a.N > 0 && a.H > 0 && a.W > 0 && a.C > 0 && a.CS >= a.C && a.CS % 16 == 0 && a.CS <= 1024, "%s: bad shape", who);
+  SPCL_CHECK_ARG(!a.dpool || (a.H >= 2 && a.W >= 2), "%s: 2x2 pooling needs H,W >= 2", who);
+  return bnrelu_bwd_run(who, dtype, a);
 }
 
-extern "C" int spcl_bnrelu_pool_backward(const void* y, const void* dact, const void* dpool, int dtype, int N, int H,
-                                         int W, int C, int CS, const float* mean, const float* invstd,
-                                         const float* scale, const float* shift, int training, float* ws,
-                                         float* dgamma, float* dbeta, void* dy, void* stream) {
-  SPCL_CHECK_ARG(y && (dact || dpool) && mean && invstd && scale && shift && ws && dgamma && dbeta && dy,
-                 "bnrelu_pool_backward: null pointer");
-  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && CS >= C && CS % 16 == 0 && CS <= 1024,
-                 "bnrelu_pool_backward: bad shape");
-  SPCL_CHECK_ARG(!dpool || (H >= 2 && W >= 2), "bnrelu_pool_backward: 2x2 pooling needs H,W >= 2");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SPCL_F32)
-    bnrelu_bwd_launch<float>(y, dact, dpool, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta,
-                             dy, st);
-  else if (dtype == SPCL_BF16)
-    bnrelu_bwd_launch<bf16_t>(y, dact, dpool, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta,
-                              dy, st);
-  else {
-    set_error("bnrelu_pool_backward: dtype %d", dtype);
-    return SPCL_EINVAL;
-  }
-  SPCL_LAUNCH_CHECK("bnrelu_pool_backward");
-  return SPCL_OK;
+extern "C" size_t spcl_bnrelu_bwd_workspace_bytes(int, int, int, int CS) { return BwdWsLayout(BwdWs::Plain, CS).bytes(); }
+
+extern "C" int spcl_bnrelu_pool_backward(const void* y, const void* dact, const void* dpool, int dtype, int N, int H, int W,
+                                         int C, int CS, const float* mean, const float* invstd, const float* scale,
+                                         const float* shift, int training, float* ws, float* dgamma, float* dbeta, void* dy,
+                                         void* stream) {
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta, stream);
+  a.grad = BnBwdArgs::arrives(dact, dpool); a.dact = dact; a.dpool = dpool; a.dy = dy;
+  return pool_backward_run("bnrelu_pool_backward", dtype, a);
 }
 
-extern "C" int spcl_bnrelu_pool_backward_strided(const void* y, const void* dact, int dact_stride, const void* dpool,
-                                                 int dtype, int N, int H, int W, int C, int CS, const float* mean,
-                                                 const float* invstd, const float* scale, const float* shift,
-                                                 int training, float* ws, float* dgamma, float* dbeta, void* dy,
-                                                 void* stream) {
+extern "C" int spcl_bnrelu_pool_backward_strided(const void* y, const void* dact, int dact_stride, const void* dpool, int dtype,
+                                                 int N, int H, int W, int C, int CS, const float* mean, const float* invstd,
+                                                 const float* scale, const float* shift, int training, float* ws, float* dgamma,
+                                                 float* dbeta, void* dy, void* stream) {
   SPCL_CHECK_ARG(dact && dact_stride >= CS && dact_stride % 8 == 0,
                  "bnrelu_pool_backward_strided: dact with a pixel stride >= CS, a multiple of 8 elements");
-  tl_dact_stride = dact_stride;
-  const int rc = spcl_bnrelu_pool_backward(y, dact, dpool, dtype, N, H, W, C, CS, mean, invstd, scale, shift, training, ws,
-                                           dgamma, dbeta, dy, stream);
-  tl_dact_stride = 0;
-  return rc;
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta, stream);
+  a.grad = BnBwdArgs::arrives(dact, dpool); a.dact = dact; a.dact_stride = dact_stride; a.dpool = dpool; a.dy = dy;
+  return pool_backward_run("bnrelu_pool_backward_strided", dtype, a);
 }
 
 // BN + ReLU backward of a block whose activation went through nn.Upsample(scale_factor=2) (unet.py:89): d_up is the gradient
 // w.r.t. the UPSAMPLED activation, [N][2H][2W][CS]; dact [N][H][W][CS] is scratch the call fills with the 2 x 2 sums
 // (= spcl_upsample2x_backward's output) on its way to the BatchNorm sums.  Results as spcl_bnrelu_pool_backward(y, dact, NULL).
 extern "C" int spcl_bnrelu_backward_up2(const void* y, const void* d_up, void* dact, int dtype, int N, int H, int W, int C,
-                                        int CS, const float* mean, const float* invstd, const float* scale,
-                                        const float* shift, int training, float* ws, float* dgamma, float* dbeta, void* dy,
-                                        void* stream) {
+                                        int CS, const float* mean, const float* invstd, const float* scale, const float* shift,
+                                        int training, float* ws, float* dgamma, float* dbeta, void* dy, void* stream) {
   SPCL_CHECK_ARG(d_up && dact, "bnrelu_backward_up2: null pointer");
   SPCL_CHECK_ARG((size_t)N * H * W * 4 < 0xffffffffull, "bnrelu_backward_up2: too many pixels");
-  tl_up2_src = d_up;
-  const int rc = spcl_bnrelu_pool_backward(y, dact, nullptr, dtype, N, H, W, C, CS, mean, invstd, scale, shift, training, ws,
-                                           dgamma, dbeta, dy, stream);
-  tl_up2_src = nullptr;
-  return rc;
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta, stream);
+  a.grad = BnGrad::Up2; a.d_up = d_up; a.dact = dact; a.dy = dy;
+  return pool_backward_run("bnrelu_backward_up2", dtype, a);
+}
+
+// BN + ReLU (+ max-pool) BACKWARD apply pass with its coefficients derived from a fixed-point accumulator block: no reduction
+// pass over the tensors where the dgrad that produced the incoming gradient filled the block (spcl_conv3x3_dgrad_bnstats_acc /
+// _poolstats_acc), and no finalize launch in any case.  Exactly one of
+//   dact    [N][H][W][CS]      gradient w.r.t. the activation; the block is already filled
+//   dpool   [N][H/2][W/2][CS]  gradient w.r.t. the pooled activation (H, W even); the block is already filled
+//   dact_nc [N][CS]            one value per (image, channel) (global average pool); THIS call's reduction pass fills the block
+// st = the forward's [4][CS] (mean, invstd, scale, shift).  The first workgroup of the apply launch writes dgamma / dbeta.
+extern "C" int spcl_bnrelu_backward_acc(const void* y, const void* dact, const void* dpool, const void* dact_nc, int dtype, int N,
+                                        int H, int W, int C, int CS, const float* st4, int training, long long* acc,
+                                        float* dgamma, float* dbeta, void* dy, void* stream) {
+  SPCL_CHECK_ARG(y && st4 && acc && dgamma && dbeta && dy, "bnrelu_backward_acc: null pointer");
+  SPCL_CHECK_ARG((dact != nullptr) + (dpool != nullptr) + (dact_nc != nullptr) == 1,
+                 "bnrelu_backward_acc: exactly one of dact, dpool, dact_nc");
+  SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && CS >= C && CS % 16 == 0 && CS <= 256, "bnrelu_backward_acc: bad shape (CS <= 256)");
+  SPCL_CHECK_ARG(!dpool || (H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0), "bnrelu_backward_acc: pooled form needs even H, W");
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, st4, training, acc, dgamma, dbeta, stream);
+  a.grad = dact_nc != nullptr ? BnGrad::PerImage : BnBwdArgs::arrives(dact, dpool);
+  a.dact = dact_nc != nullptr ? dact_nc : dact; a.dpool = dpool; a.dy = dy;
+  a.sums = dact_nc != nullptr ? BnSums::Fill : BnSums::Filled;
+  return bnrelu_bwd_run("bnrelu_backward_acc", dtype, a);
 }
 
 // BN + ReLU (+ max-pool) backward whose reduction pass ADDS its sums to a (zeroed) fixed-point accumulator block and whose
@@ -1940,22 +1997,10 @@ extern "C" int spcl_bnrelu_backward_fill_acc(const void* y, void* dact, int dact
   SPCL_CHECK_ARG(dact_stride == 0 || (dact && dact_stride >= CS && dact_stride % 8 == 0 && !d_up),
                  "bnrelu_backward_fill_acc: dact with a pixel stride >= CS, a multiple of 8 elements");
   SPCL_CHECK_ARG(!d_up || (dact && !dpool && (size_t)N * H * W * 4 < 0xffffffffull), "bnrelu_backward_fill_acc: the x2 form takes d_up + scratch dact");
-  hipStream_t st = (hipStream_t)stream;
-  const float *mean = st4, *invstd = st4 + CS, *scale = st4 + 2 * CS, *shift = st4 + 3 * CS;
-  tl_acc_fill = true;
-  tl_dact_stride = dact_stride;
-  tl_up2_src = d_up;
-  if (dtype == SPCL_F32)
-    bnrelu_bwd_launch<float>(y, dact, dpool, N, H, W, C, CS, mean, invstd, scale, shift, training, nullptr, dgamma, dbeta, dy, st,
-                             nullptr, nullptr, nullptr, 0, false, acc);
-  else
-    bnrelu_bwd_launch<bf16_t>(y, dact, dpool, N, H, W, C, CS, mean, invstd, scale, shift, training, nullptr, dgamma, dbeta, dy, st,
-                              nullptr, nullptr, nullptr, 0, false, acc);
-  tl_acc_fill = false;
-  tl_dact_stride = 0;
-  tl_up2_src = nullptr;
-  SPCL_LAUNCH_CHECK("bnrelu_backward_fill_acc");
-  return SPCL_OK;
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, st4, training, acc, dgamma, dbeta, stream);
+  a.grad = d_up != nullptr ? BnGrad::Up2 : BnBwdArgs::arrives(dact, dpool); a.sums = BnSums::Fill;
+  a.dact = dact; a.dact_stride = dact_stride; a.dpool = dpool; a.d_up = d_up; a.dy = dy;
+  return bnrelu_bwd_run("bnrelu_backward_fill_acc", dtype, a);
 }
 
 // ... and for a gradient whose sums came as per-tile ROWS [nrows][2][CS] (sum dz, sum dz (y - mean): the dgrad epilogues of
@@ -1970,19 +2015,10 @@ extern "C" int spcl_bnrelu_backward_rows_acc(const void* y, const void* dact, co
   SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && CS >= C && CS % 16 == 0 && CS <= 256 && nrows > 0,
                  "bnrelu_backward_rows_acc: bad shape (CS <= 256)");
   SPCL_CHECK_ARG(!dpool || (H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0), "bnrelu_backward_rows_acc: pooled form needs even H, W");
-  SPCL_CHECK_ARG(dtype == SPCL_BF16 || dtype == SPCL_F32, "bnrelu_backward_rows_acc: dtype %d", dtype);
-  hipStream_t st = (hipStream_t)stream;
-  const float *mean = st4, *invstd = st4 + CS, *scale = st4 + 2 * CS, *shift = st4 + 3 * CS;
-  tl_acc_fill = true;
-  if (dtype == SPCL_F32)
-    bnrelu_bwd_launch<float>(y, dact, dpool, N, H, W, C, CS, mean, invstd, scale, shift, training, nullptr, dgamma, dbeta, dy, st,
-                             nullptr, nullptr, rows, nrows, false, acc);
-  else
-    bnrelu_bwd_launch<bf16_t>(y, dact, dpool, N, H, W, C, CS, mean, invstd, scale, shift, training, nullptr, dgamma, dbeta, dy, st,
-                              nullptr, nullptr, rows, nrows, false, acc);
-  tl_acc_fill = false;
-  SPCL_LAUNCH_CHECK("bnrelu_backward_rows_acc");
-  return SPCL_OK;
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, st4, training, acc, dgamma, dbeta, stream);
+  a.grad = BnBwdArgs::arrives(dact, dpool); a.dact = dact; a.dpool = dpool; a.dy = dy;
+  a.sums = BnSums::Rows; a.rows = rows; a.nrows = nrows;
+  return bnrelu_bwd_run("bnrelu_backward_rows_acc", dtype, a);
 }
 
 // BN + ReLU backward for a gradient that is the same for every pixel of an image: dact_nc [N][CS] of dtype (what
@@ -1994,53 +2030,32 @@ extern "C" int spcl_bnrelu_backward_bcast(const void* y, const void* dact_nc, in
   SPCL_CHECK_ARG(y && dact_nc && mean && invstd && scale && shift && ws && dgamma && dbeta && dy,
                  "bnrelu_backward_bcast: null pointer");
   SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && CS >= C && CS % 16 == 0 && CS <= 1024, "bnrelu_backward_bcast: bad shape");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SPCL_F32)
-    bnrelu_bwd_launch<float>(y, dact_nc, nullptr, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta,
-                             dy, st, nullptr, nullptr, nullptr, 0, true);
-  else if (dtype == SPCL_BF16)
-    bnrelu_bwd_launch<bf16_t>(y, dact_nc, nullptr, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta,
-                              dy, st, nullptr, nullptr, nullptr, 0, true);
-  else {
-    set_error("bnrelu_backward_bcast: dtype %d", dtype);
-    return SPCL_EINVAL;
-  }
-  SPCL_LAUNCH_CHECK("bnrelu_backward_bcast");
-  return SPCL_OK;
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta, stream);
+  a.grad = BnGrad::PerImage; a.dact = dact_nc; a.dy = dy;
+  return bnrelu_bwd_run("bnrelu_backward_bcast", dtype, a);
 }
 
-extern "C" size_t spcl_bnrelu_image_wgrad_workspace_bytes(int N, int H, int W, int CS) {
-  return spcl_bnrelu_bwd_workspace_bytes(N, H, W, CS) + ((size_t)IMG_WGRAD_WG * 9 * CS + (size_t)W) * sizeof(float);
+extern "C" size_t spcl_bnrelu_image_wgrad_workspace_bytes(int, int, int W, int CS) {
+  return BwdWsLayout(BwdWs::ImageWgrad, CS, W).bytes();
 }
 
-extern "C" int spcl_bnrelu_backward_image_wgrad(const void* y, const void* dact, const float* image, int dtype, int N,
-                                                int H, int W, int C, int CS, const float* mean, const float* invstd,
-                                                const float* scale, const float* shift, int training, float* ws,
-                                                float* dgamma, float* dbeta, float* dw, void* stream) {
+extern "C" int spcl_bnrelu_backward_image_wgrad(const void* y, const void* dact, const float* image, int dtype, int N, int H,
+                                                int W, int C, int CS, const float* mean, const float* invstd, const float* scale,
+                                                const float* shift, int training, float* ws, float* dgamma, float* dbeta,
+                                                float* dw, void* stream) {
   SPCL_CHECK_ARG(y && dact && image && mean && invstd && scale && shift && ws && dgamma && dbeta && dw,
                  "bnrelu_backward_image_wgrad: null pointer");
   SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && CS >= C && CS % 16 == 0 && CS <= 256 && (CS & (CS - 1)) == 0,
                  "bnrelu_backward_image_wgrad: bad shape (CS must be a power of two in 16..256)");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SPCL_F32)
-    bnrelu_bwd_launch<float>(y, dact, nullptr, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta,
-                             nullptr, st, image, dw);
-  else if (dtype == SPCL_BF16)
-    bnrelu_bwd_launch<bf16_t>(y, dact, nullptr, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma,
-                              dbeta, nullptr, st, image, dw);
-  else {
-    set_error("bnrelu_backward_image_wgrad: dtype %d", dtype);
-    return SPCL_EINVAL;
-  }
-  SPCL_LAUNCH_CHECK("bnrelu_backward_image_wgrad");
-  return SPCL_OK;
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta, stream);
+  a.dact = dact; a.out = BnOut::ImageWgrad; a.img = image; a.dw = dw;
+  return bnrelu_bwd_run("bnrelu_backward_image_wgrad", dtype, a);
 }
 
-
 extern "C" int spcl_bnrelu_backward_rows(const void* y, const void* dact, const float* image, const float* rows, int nrows,
-                                         int dtype, int N, int H, int W, int C, int CS, const float* mean,
-                                         const float* invstd, const float* scale, const float* shift, int training,
-                                         float* ws, float* dgamma, float* dbeta, void* dy, float* dw, void* stream) {
+                                         int dtype, int N, int H, int W, int C, int CS, const float* mean, const float* invstd,
+                                         const float* scale, const float* shift, int training, float* ws, float* dgamma,
+                                         float* dbeta, void* dy, float* dw, void* stream) {
   SPCL_CHECK_ARG(y && dact && rows && mean && invstd && scale && shift && ws && dgamma && dbeta,
                  "bnrelu_backward_rows: null pointer");
   SPCL_CHECK_ARG((image != nullptr) == (dw != nullptr) && (image != nullptr) != (dy != nullptr),
@@ -2049,19 +2064,28 @@ extern "C" int spcl_bnrelu_backward_rows(const void* y, const void* dact, const 
                  "bnrelu_backward_rows: bad shape");
   SPCL_CHECK_ARG(image == nullptr || (CS <= 256 && (CS & (CS - 1)) == 0), "bnrelu_backward_rows: image path needs CS "
                  "a power of two in 16..256");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SPCL_F32)
-    bnrelu_bwd_launch<float>(y, dact, nullptr, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta, dy,
-                             st, image, dw, rows, nrows);
-  else if (dtype == SPCL_BF16)
-    bnrelu_bwd_launch<bf16_t>(y, dact, nullptr, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta,
-                              dy, st, image, dw, rows, nrows);
-  else {
-    set_error("bnrelu_backward_rows: dtype %d", dtype);
-    return SPCL_EINVAL;
-  }
-  SPCL_LAUNCH_CHECK("bnrelu_backward_rows");
-  return SPCL_OK;
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta, stream);
+  a.dact = dact; a.sums = BnSums::Rows; a.rows = rows; a.nrows = nrows;
+  a.out = image != nullptr ? BnOut::ImageWgrad : BnOut::Dy; a.dy = dy; a.img = image; a.dw = dw;
+  return bnrelu_bwd_run("bnrelu_backward_rows", dtype, a);
+}
+
+// BN + ReLU + 2x2 max-pool backward finished from per-tile rows that came with the dgrad producing dpool
+// (spcl_conv3x3_dgrad_poolstats): final reduction of the rows -> coefficients -> the apply pass.  No `dact` here: a block
+// whose activation is also consumed directly (skip connection, hook tap) keeps the two-pass path.
+extern "C" int spcl_bnrelu_pool_backward_rows(const void* y, const void* dpool, const float* rows, int nrows, int dtype, int N,
+                                              int H, int W, int C, int CS, const float* mean, const float* invstd,
+                                              const float* scale, const float* shift, int training, float* ws, float* dgamma,
+                                              float* dbeta, void* dy, void* stream) {
+  SPCL_CHECK_ARG(y && dpool && rows && mean && invstd && scale && shift && ws && dgamma && dbeta && dy,
+                 "bnrelu_pool_backward_rows: null pointer");
+  SPCL_CHECK_ARG(N > 0 && H >= 2 && W >= 2 && C > 0 && CS >= C && CS % 16 == 0 && CS <= 1024 && nrows > 0,
+                 "bnrelu_pool_backward_rows: bad shape");
+  SPCL_CHECK_ARG(dtype == SPCL_BF16,
+                 "bnrelu_pool_backward_rows: dtype %d (bf16 only: the rows come from the specialised dgrad kernels)", dtype);
+  BnBwdArgs a = bwd_args(y, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta, stream);
+  a.grad = BnGrad::Pooled; a.dpool = dpool; a.dy = dy; a.sums = BnSums::Rows; a.rows = rows; a.nrows = nrows;
+  return bnrelu_bwd_run("bnrelu_pool_backward_rows", dtype, a);
 }
 
 // ---- image3: BN + ReLU backward of the FIRST conv of a one-channel-image block and that conv's weight gradient, finished
@@ -2082,23 +2106,21 @@ extern "C" int spcl_image_autocorr(const float* image, int N, int H, int W, floa
   return SPCL_OK;
 }
 
-extern "C" size_t spcl_bnrelu_image3_workspace_bytes(int CS) {
-  return ((size_t)BWD_MAX_WG * 11 * CS + 2 * (size_t)CS + ACORR_FOLD * 64) * sizeof(float);
-}
+extern "C" size_t spcl_bnrelu_image3_workspace_bytes(int CS) { return BwdWsLayout(BwdWs::Image3, CS).bytes(); }
 
 extern "C" int spcl_bnrelu_backward_rows_image3(const float* rows11, int nrows, const float* acorr, int nacorr,
-                                                const float* w_oihw, int N, int H, int W, int C, int CS,
-                                                const float* mean, const float* invstd, const float* scale,
-                                                int training, float* ws, float* dgamma, float* dbeta, float* dw,
-                                                void* stream) {
+                                                const float* w_oihw, int N, int H, int W, int C, int CS, const float* mean,
+                                                const float* invstd, const float* scale, int training, float* ws, float* dgamma,
+                                                float* dbeta, float* dw, void* stream) {
   SPCL_CHECK_ARG(rows11 && acorr && w_oihw && mean && invstd && scale && ws && dgamma && dbeta && dw,
                  "bnrelu_backward_rows_image3: null pointer");
   SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && CS >= C && CS % 16 == 0 && CS <= 256 && nrows > 0 && nacorr > 0,
                  "bnrelu_backward_rows_image3: bad shape");
   hipStream_t st = (hipStream_t)stream;
-  float* partial = ws;                             // [nwg][11][CS]
-  float* ab = ws + (size_t)BWD_MAX_WG * 11 * CS;   // [2][CS]: the folded coefficients (kept for symmetry with the other paths)
-  float* afold = ab + 2 * (size_t)CS;              // [ACORR_FOLD][64]
+  const BwdWsLayout l(BwdWs::Image3, CS);
+  float* partial = ws + l.partial;  // [nwg][11][CS]
+  float* ab = ws + l.ab;            // [2][CS]: the folded coefficients (kept for symmetry with the other paths)
+  float* afold = ws + l.afold;      // [ACORR_FOLD][64]
   const float* fin_src = rows11;
   int nwg = nrows, transposed = 0;
   constexpr int IMG3_ROWS = 1024;  // the final kernel walks eleven strided sums per channel: four rows per thread
@@ -2127,17 +2149,16 @@ extern "C" int spcl_bnrelu_backward_rows_image3(const float* rows11, int nrows, 
 // ... from ONE row set per workgroup of spcl_conv16_bwd_fused, already in the final kernel's layout
 // ([sub-row 11][channel CS][workgroup]) and with the autocorrelation rows already folded: the final kernel alone
 extern "C" int spcl_bnrelu_backward_wgrows_image3(const float* wg_rows, int nwg, const float* acorr, int nacorr,
-                                                  const float* w_oihw, int N, int H, int W, int C, int CS,
-                                                  const float* mean, const float* invstd, const float* scale,
-                                                  int training, float* ws, float* dgamma, float* dbeta, float* dw,
-                                                  void* stream) {
+                                                  const float* w_oihw, int N, int H, int W, int C, int CS, const float* mean,
+                                                  const float* invstd, const float* scale, int training, float* ws, float* dgamma,
+                                                  float* dbeta, float* dw, void* stream) {
   SPCL_CHECK_ARG(wg_rows && acorr && w_oihw && mean && invstd && scale && ws && dgamma && dbeta && dw,
                  "bnrelu_backward_wgrows_image3: null pointer");
   SPCL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && CS >= C && CS % 16 == 0 && CS <= 256 && nwg > 0 && nacorr > 0 &&
                      nacorr <= 64,
                  "bnrelu_backward_wgrows_image3: bad shape");
   hipStream_t st = (hipStream_t)stream;
-  float* ab = ws + (size_t)BWD_MAX_WG * 11 * CS;
+  float* ab = ws + BwdWsLayout(BwdWs::Image3, CS).ab;
   const Image3Args im{acorr, nacorr, w_oihw, dw};
   prof_cost((double)nwg * 11 * CS * 4.0, 0.0);
   SPCL_LAUNCH(bnrelu_bwd_fin_kernel, dim3(3 * CS), dim3(256), 0, st, wg_rows, nwg, C, CS, (float)((size_t)N * H * W), training,
@@ -2145,27 +2166,3 @@ extern "C" int spcl_bnrelu_backward_wgrows_image3(const float* wg_rows, int nwg,
   SPCL_LAUNCH_CHECK("bnrelu_backward_wgrows_image3");
   return SPCL_OK;
 }
-
-// BN + ReLU + 2x2 max-pool backward finished from per-tile rows that came with the dgrad producing dpool
-// (spcl_conv3x3_dgrad_poolstats): final reduction of the rows -> coefficients -> the apply pass.  No `dact` here: a block
-// whose activation is also consumed directly (skip connection, hook tap) keeps the two-pass path.
-extern "C" int spcl_bnrelu_pool_backward_rows(const void* y, const void* dpool, const float* rows, int nrows, int dtype,
-                                              int N, int H, int W, int C, int CS, const float* mean, const float* invstd,
-                                              const float* scale, const float* shift, int training, float* ws,
-                                              float* dgamma, float* dbeta, void* dy, void* stream) {
-  SPCL_CHECK_ARG(y && dpool && rows && mean && invstd && scale && shift && ws && dgamma && dbeta && dy,
-                 "bnrelu_pool_backward_rows: null pointer");
-  SPCL_CHECK_ARG(N > 0 && H >= 2 && W >= 2 && C > 0 && CS >= C && CS % 16 == 0 && CS <= 1024 && nrows > 0,
-                 "bnrelu_pool_backward_rows: bad shape");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SPCL_BF16)
-    bnrelu_bwd_launch<bf16_t>(y, nullptr, dpool, N, H, W, C, CS, mean, invstd, scale, shift, training, ws, dgamma, dbeta,
-                              dy, st, nullptr, nullptr, rows, nrows);
-  else {
-    set_error("bnrelu_pool_backward_rows: dtype %d (bf16 only: the rows come from the specialised dgrad kernels)", dtype);
-    return SPCL_EINVAL;
-  }
-  SPCL_LAUNCH_CHECK("bnrelu_pool_backward_rows");
-  return SPCL_OK;
-}
-

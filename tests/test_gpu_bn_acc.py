@@ -567,3 +567,73 @@ def test_second_backward_through_the_same_graph_falls_back_to_rows():
     for k, p in enc:
         a, b = p.grad.double(), first[k].double()
         assert torch.isfinite(a).all() and float((a - b).norm() / b.norm().clamp_min(1e-30)) < 2e-2, k
+
+
+# ---- the forward entry points that write the activation somewhere else than a dense tensor, bit for bit against
+# spcl_bnrelu_pool_forward (itself pinned to float64 in test_gpu_kernels.py): no tolerance
+SENTINEL = -77.0  # (exact in bf16; relu never produces it)
+PLACED_SHAPES = [(2, 6, 10, 32), (1, 5, 7, 16)]
+
+
+def _placed_inputs(N, H, W, cs, dtype):
+    g = torch.Generator().manual_seed(cs + H)
+    y = (torch.randn(N, H, W, cs, generator=g) * 1.2 + 0.1).to(dtype).cuda()
+    return y, (torch.rand(cs, generator=g) + 0.5).cuda(), (torch.randn(cs, generator=g) * 0.3).cuda()
+
+
+def _dense_forward(n, y, scale, shift, with_pool):
+    N, H, W, cs = y.shape
+    act = torch.full_like(y, SENTINEL)
+    pool = torch.full((N, H // 2, W // 2, cs), SENTINEL, dtype=y.dtype, device="cuda") if with_pool else None
+    n.call("spcl_bnrelu_pool_forward", n.ptr(y), n.dtype_code(y.dtype), N, H, W, cs, n.ptr(scale), n.ptr(shift), n.ptr(act),
+           n.ptr(pool), n.stream())
+    return act, pool
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("N,H,W,cs", PLACED_SHAPES)
+def test_strided_forward_writes_the_dense_bits_into_its_half_and_no_stride_outlives_its_call(N, H, W, cs, dtype):
+    """spcl_bnrelu_pool_forward_strided into the upper half of a [N][H][W][2 CS] buffer: that half equals the dense output,
+    the lower half keeps the sentinel, the pooled output is equal too -- with and without pool_out; then dense, strided, dense,
+    a REFUSED strided call (stride CS - 8), dense: every dense result equals the first"""
+    n = _n()
+    y, scale, shift = _placed_inputs(N, H, W, cs, dtype)
+
+    def strided(with_pool, stride):
+        wide = torch.full((N, H, W, 2 * cs), SENTINEL, dtype=dtype, device="cuda")
+        pool = torch.full((N, H // 2, W // 2, cs), SENTINEL, dtype=dtype, device="cuda") if with_pool else None
+        rc = n.lib().spcl_bnrelu_pool_forward_strided(n.ptr(y), n.dtype_code(dtype), N, H, W, cs, n.ptr(scale), n.ptr(shift),
+                                                      n.ptr(wide[..., cs:]), stride, n.ptr(pool), n.stream())
+        return rc, wide, pool
+
+    for with_pool in (False, True):
+        act0, pool0 = _dense_forward(n, y, scale, shift, with_pool)
+        rc, wide, pool1 = strided(with_pool, 2 * cs)
+        assert rc == 0
+        assert torch.equal(wide[..., cs:], act0)
+        assert bool((wide[..., :cs] == SENTINEL).all())
+        if with_pool:
+            assert torch.equal(pool1, pool0)
+    first = _dense_forward(n, y, scale, shift, True)
+    assert strided(True, 2 * cs)[0] == 0
+    second = _dense_forward(n, y, scale, shift, True)
+    rc, wide, pool1 = strided(True, cs - 8)
+    assert rc != 0 and bool((wide == SENTINEL).all()) and bool((pool1 == SENTINEL).all())
+    third = _dense_forward(n, y, scale, shift, True)
+    for act, pool in (second, third):
+        assert torch.equal(act, first[0]) and torch.equal(pool, first[1])
+        assert not bool((act == SENTINEL).any())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("N,H,W,cs", PLACED_SHAPES)
+def test_up2_forward_repeats_the_dense_activation_over_every_2x2_block(N, H, W, cs, dtype):
+    """spcl_bnrelu_up2_forward: up[n, 2h + a, 2w + b, :] equals the dense activation for all four (a, b)"""
+    n = _n()
+    y, scale, shift = _placed_inputs(N, H, W, cs, dtype)
+    act0, _ = _dense_forward(n, y, scale, shift, False)
+    up = torch.full((N, 2 * H, 2 * W, cs), SENTINEL, dtype=dtype, device="cuda")
+    n.call("spcl_bnrelu_up2_forward", n.ptr(y), n.dtype_code(dtype), N, H, W, cs, n.ptr(scale), n.ptr(shift), n.ptr(up), n.stream())
+    for a in (0, 1):
+        for b in (0, 1):
+            assert torch.equal(up[:, a::2, b::2, :], act0), (a, b)
