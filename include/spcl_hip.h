@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 24
+#define SPCL_ABI_VERSION 25
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -562,6 +562,23 @@ int spcl_conv16_bwd_fused_image(const void* dy, int dtype, int N, int H, int W, 
                                 const void* w_packed_image, const float* scale2, const float* shift2, const float* mean2,
                                 const float* image, float* rows11, float* partial, float* dw_oihw, int Cin, int Cout,
                                 float* wg_rows, const float* acorr, int nacorr, float* acorr16, void* stream);
+/* spcl_conv16_bwd_fused_image whose incoming gradient dy is never stored either: the block's output goes through
+ * nn.BatchNorm2d / nn.ReLU (unet.py:75-77) and nn.MaxPool2d(2, 2) (unet.py:118-121) only, so dy is the autograd backward of
+ * those three applied to dpool -- what spcl_bnrelu_backward_rows_acc(y, dact = NULL, dpool, rows, ..) writes.  The call takes
+ * that call's inputs in dy's place: y [N][H][W][16] (this convolution's raw output), dpool [N][H/2][W/2][16], the per-tile
+ * rows [nrows][2][16] of the BatchNorm's backward sums, its forward st4 [4][16] and its ZEROED accumulator block acc.  One
+ * small launch adds the rows to the block (as there); the one-pass kernel derives the BatchNorm's folded coefficients from it,
+ * forms dy per tile in its loader -- bit for bit the tensor the apply pass would have written, zero outside the image -- and
+ * its first workgroup writes dgamma / dbeta [16].  Every other argument and output as spcl_conv16_bwd_fused_image.
+ * _supported: training mode, bf16, 16 -> 16 channels, H and W multiples of 14 (hence even), the row-mapped two-wave kernel,
+ * one image under 2 GiB. */
+int spcl_conv16_bwd_fused_image_pooled_supported(int dtype, int N, int H, int W, int CinK, int CoutS, int training);
+int spcl_conv16_bwd_fused_image_pooled(const void* y, const void* dpool, const float* rows, int nrows, int dtype, int N, int H,
+                                       int W, const float* st4, int training, long long* acc, float* dgamma, float* dbeta,
+                                       const void* w_packed_dgrad, const void* w_packed_image, const float* scale2,
+                                       const float* shift2, const float* mean2, const float* image, float* rows11,
+                                       float* partial, float* dw_oihw, int Cin, int Cout, float* wg_rows, const float* acorr,
+                                       int nacorr, float* acorr16, void* stream);
 int spcl_bnrelu_backward_wgrows_image3(const float* wg_rows, int nwg, const float* acorr, int nacorr, const float* w_oihw,
                                        int N, int H, int W, int C, int CS, const float* mean, const float* invstd,
                                        const float* scale, int training, float* ws, float* dgamma, float* dbeta,

@@ -7,6 +7,7 @@
 #include "bn_acc.hpp"
 #include "common.hpp"
 #include "image_acorr.hpp"
+#include "pool_dy.hpp"
 
 namespace spcl {
 
@@ -262,24 +263,7 @@ __global__ __launch_bounds__(256) void bn_eval_affine_multi_kernel(BnEvalItems p
 //   non-pool: positions are pixels, the tensors are walked linearly;
 //   pool:     positions are 2x2 windows on the CEIL grid, walked row by row (torch.max_pool2d floors: a window cut by
 //             an odd edge produces no pooled value, but its pixels still get their activation / gradient).
-template <typename T> struct Word;  // one 32-bit word of a packed chunk
-template <> struct Word<float> {
-  static constexpr int EPW = 1;
-  static __device__ __forceinline__ float get(uint32_t w, int) { return __uint_as_float(w); }
-  static __device__ __forceinline__ uint32_t make(const float* v) { return __float_as_uint(v[0]); }
-  // element h of the result = element h of raw word s[h]
-  static __device__ __forceinline__ uint32_t merge(const uint32_t* s) { return s[0]; }
-};
-template <> struct Word<bf16_t> {
-  static constexpr int EPW = 2;
-  static __device__ __forceinline__ float get(uint32_t w, int h) {
-    return __uint_as_float(h ? (w & 0xffff0000u) : (w << 16));
-  }
-  static __device__ __forceinline__ uint32_t make(const float* v) {
-    return (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
-  }
-  static __device__ __forceinline__ uint32_t merge(const uint32_t* s) { return (s[0] & 0x0000ffffu) | (s[1] & 0xffff0000u); }
-};
+// (Word<T>, one 32-bit word of a packed chunk: pool_dy.hpp)
 
 template <int EPC> __device__ __forceinline__ void load_coef(float* dst, const float* src, int cc) {
 #pragma unroll
@@ -969,25 +953,10 @@ __global__ __launch_bounds__(256, 3) BWD_POOL_WPE void bnrelu_bwd_pool_kernel(co
             if (APPLY && FAST) {
               // the training step's case, written for the instruction count (this kernel is the step's largest symbol: 4
               // launches, 79 us, its vector port 63 % busy beside 0.69 of the HBM peak): whole windows, pooled gradient only.
-              // The first maximum of relu(z) in scan order as LANE MASKS -- z_k > (running maximum, >= 0) for k = 1 .. 3,
-              // combined by scalar and-nots -- instead of a tracked index and four index compares: 30 vector instructions
-              // per (window, channel) for 44.  Same values: dz_k = dp at that pixel if its z > 0, else 0; o = fma(sc, dz, X).
-              float yk[4], z[4];
-#pragma unroll
-              for (int k = 0; k < 4; ++k) {
-                yk[k] = Word<T>::get(w.ry[k][wi], h);
-                z[k] = fmaf(sc[e], yk[k], sh[e]);
-              }
-              float m = fmaxf(z[0], 0.f);
-              const bool s1 = z[1] > m;
-              m = fmaxf(m, z[1]);
-              const bool s2 = z[2] > m;
-              m = fmaxf(m, z[2]);
-              const bool s3 = z[3] > m;
-              const bool b[4] = {z[0] > 0.f && !s1 && !s2 && !s3, s1 && !s2 && !s3, s2 && !s3, s3};
-              const float dp = Word<T>::get(rdp[wi], h);
-#pragma unroll
-              for (int k = 0; k < 4; ++k) o[k][h] = fmaf(sc[e], b[k] ? dp : 0.f, fmaf(c0[e], yk[k], c1[e]));
+              // The expression sequence is pool_dy.hpp's (shared with conv16_bwd.hip's POOLDY loader, which must form the same
+              // bits): the first maximum of relu(z) in scan order as lane masks, 30 vector instructions per (window, channel)
+              // for the 44 of a tracked index.  Same values: dz_k = dp at that pixel if its z > 0, else 0; o = fma(sc, dz, X).
+              SPCL_POOL_WINDOW_DY(T, w.ry, rdp, wi, h, sc[e], sh[e], c0[e], c1[e], o)
               continue;
             }
             float yk[4], dz[4];
@@ -1222,6 +1191,14 @@ __global__ __launch_bounds__(256) void bwd_rows_acc_kernel(const float* __restri
     }
     if (p == 0 && o < NW4) bn_acc_add_word(acc, CS, w & (BN_ACC_REPLICAS - 1), c, which, limb, s);
   }
+}
+
+// (its one launch site: this file's rows paths and conv16_bwd.hip's pooled entry) -> workgroups launched
+int launch_bwd_rows_acc(const float* rows, int nrows, int CS, long long* acc, hipStream_t st) {
+  const int G = (nrows + 511) / 512;
+  const int nwg = (nrows + G - 1) / G;
+  SPCL_LAUNCH(bwd_rows_acc_kernel, dim3(nwg), dim3(256), 0, st, rows, nrows, G, CS, acc);
+  return nwg;
 }
 
 // ---- pass 2, no pooling (linear): dy = scale*dz + A*y + B
@@ -1573,9 +1550,7 @@ static BwdSums bnrelu_bwd_sums(const BnBwdArgs& a, float* partial) {
   if (a.sums == BnSums::Rows) {
     static const int fin_rows = lab_env("SPCL_BWD_FIN_MAX_ROWS", BWD_MAX_WG);
     if (a.acc != nullptr) {  // ... go into the block: <= 512 workgroups add, the apply pass derives
-      const int G = (a.nrows + 511) / 512;
-      s.nwg = (a.nrows + G - 1) / G;
-      SPCL_LAUNCH(bwd_rows_acc_kernel, dim3(s.nwg), dim3(256), 0, a.st, a.rows, a.nrows, G, a.CS, a.acc);
+      s.nwg = launch_bwd_rows_acc(a.rows, a.nrows, a.CS, a.acc, a.st);
     } else if (a.nrows <= fin_rows) {  // the finalize launch reads them where they are
       s.fin_src = a.rows;
       s.nwg = a.nrows;

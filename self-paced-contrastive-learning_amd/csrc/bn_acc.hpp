@@ -73,6 +73,10 @@ struct BnAccBwd {
 };
 
 #ifdef __HIPCC__
+// per-tile rows [nrows][2][CS] of a BatchNorm's backward sums ADDED to its zeroed block by one small launch (bn.hip
+// bwd_rows_acc_kernel) -> the workgroups launched
+int launch_bwd_rows_acc(const float* rows, int nrows, int CS, long long* acc, hipStream_t st);
+
 __device__ __forceinline__ void bn_acc_atomic_add(long long* p, long long v) {
   // (result unused: a no-return global_atomic_add_x2, performed at the memory side)
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

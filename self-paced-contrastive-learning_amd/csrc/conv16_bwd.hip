@@ -30,7 +30,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
+#include "bn_acc.hpp"
 #include "conv_common.hpp"
+#include "pool_dy.hpp"
 
 namespace spcl {
 
@@ -56,6 +58,11 @@ struct Bwd16Args {
   int dbg;  // ablation bits (timing experiments only, wrong results; 0 in production): 1 no dgrad MFMAs, 2 no pixel pass,
             // 4 no weight-gradient phase, 8 no dz / tap sums, 16 no global requests after the first tile
   unsigned long long* stamps;  // debug (SPCL_CONV16_STAMPS=1): s_memtime ticks of wave 0 per phase, summed over its tiles
+  // POOLDY (conv16_bwd_rows_kernel): dy == null, never materialised -- the layer's output sits behind BatchNorm + ReLU + a
+  // 2 x 2 max-pool and the loader forms dy per tile from
+  const unsigned char* yb;     // [N][H][W][16] bf16, the raw output of THIS convolution,
+  const unsigned char* dpool;  // [N][H/2][W/2][16] bf16, the gradient of the pooled activation, and
+  BnAccBwd bw;                 // that BatchNorm's backward sums (bn_acc.hpp; bw.st: its forward [4][16])
 };
 
 constexpr int B16_TH = 14, B16_TW = 14, B16_HW = 16, B16_RP = 22, B16_PS = 32;
@@ -538,15 +545,35 @@ constexpr int R16_ACC = R16_RED + 512;
 constexpr int R16_TRASH = R16_ACC + 576;
 constexpr int R16_TAB = R16_TRASH + 32;        // [4 k-groups][8] dwords: (tap, chunk) byte offsets of the five k-steps
 constexpr int B16_LDS_ROWS = R16_TAB + 128;    // 19 168
+constexpr int R16_CF = B16_LDS_ROWS;           // POOLDY: [4][16] f32: A, B, scale, shift of the layer's own BatchNorm
+constexpr int B16_LDS_POOLDY = R16_CF + 256;   // 19 424: eight workgroups per CU still fit (155 392 of 163 840 bytes)
 
+// POOLDY: dy does not exist either (Bwd16Args::dy == null).  The layer's output goes through BatchNorm + ReLU + a 2 x 2
+// max-pool and nothing else (the encoder's first block: unet.py:75-77, 118-121), so its gradient is
+//   dy_k = scale dz_k + A y_k + B,   dz_k = dpool at the window's first maximum of relu(z) if that z > 0, else 0
+// -- what bn.hip bnrelu_bwd_pool_kernel<bf16, APPLY, FAST, ACC> wrote to a tensor this kernel was its only reader of (103 MB
+// at 64 x 224^2, written once and read once).  Here the loader forms it per tile: the tile origin is even, so the 16 x 16 dy
+// halo (rows y0 - 1 .. y0 + 14) lies inside the 9 x 9 whole windows from (y0 - 2, x0 - 2) on.  A work item is (window, 8-channel
+// half): four 16-byte loads of y and one of dpool, pool_dy.hpp's expression sequence (the apply kernel's: same bits), and up to
+// four 16-byte LDS stores at the addresses the dy halo's stores had -- only the window's pixels inside the halo are stored.
+// A window outside the image gives exact zeros (the transposed convolution's zero padding, never A 0 + B); with even H, W a
+// window is inside or outside as a whole.  162 items on 128 threads: items 0 .. 127 = the thread index, requested a tile
+// period ahead like the dy halo was (five 16-byte requests for its four); items 128 .. 161 are wave 1's lanes 0 .. 33 (wave 0
+// has the tap sums at the tile's end to itself), requested inside the tile behind the first item.  A, B come from the BatchNorm's accumulator block
+// in the prologue with bn_acc_bwd_channel, as the apply kernel derived them (the launch's first workgroup writes dgamma /
+// dbeta), and wait in LDS with scale / shift: 32 coefficients per thread are read per tile, not carried over it.
 // RECOMP: y2 does not exist (Bwd16Args::y2 == null).  The pixel pass forms it from the image copies that sit in LDS for the tap
 // sums: one v_mfma_f32_16x16x16_bf16 per tile row with conv_fast.hip conv3x3_image_kernel's operands -- A = the 1 -> 16 filters
 // (row = cout r16, k-group = ky), B = (x[q], x[q + 1], x[q + 2], finite pad) of pixel column q from the copy of q's parity --
 // rounded by the same conversion: the bits that kernel would have stored, in the registers the y2 requests used to fill (D:
 // couts 4 g .. + 3 of pixel column r16).  Seven loads per tile and wave fewer, seven small MFMAs more; whole tiles only.
-template <bool SHIFTED, bool WGROWS, bool RECOMP = false>
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHIFTED)))) void conv16_bwd_rows_kernel(Bwd16Args a) {
+template <bool SHIFTED, bool WGROWS, bool RECOMP = false, bool POOLDY = false>
+// (POOLDY with per-tile rows -- not the training step's form, which is WGROWS: 118 registers, four waves -- asked for four waves
+// per SIMD takes all 128 registers and 28 bytes of scratch; asked for three, like the shifted form, it comes out at 127
+// without scratch: four are resident all the same)
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHIFTED || (POOLDY && !WGROWS))))) void conv16_bwd_rows_kernel(Bwd16Args a) {
   static_assert(!(RECOMP && SHIFTED), "y2 from the image: whole 14 x 14 tiles");
+  static_assert(!POOLDY || RECOMP, "dy from y and dpool: whole 14 x 14 tiles of the recomputing form (even H, W)");
   constexpr int NW = 2;
   constexpr int TH = B16_TH, TW = B16_TW, HW_ = B16_HW, RP = R16_RP, PS = B16_PS;
   constexpr int NSTEPS = 5, NTHR = 64 * NW, ITER = 512 / NTHR, RPI = NTHR / 32;
@@ -612,12 +639,24 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
   }
   if (WGROWS)
     for (int i = t0; i < (512 + 576) / 4; i += NTHR) ((float*)(lds + R16_RED))[i] = 0.f;
+  if (POOLDY && t0 < 16) {  // the layer's own BatchNorm backward: A, B of channel t0 from the block (bn.hip acc_coef_bwd's steps)
+    BnAccBwdRaw raw;
+    raw.load(a.bw, t0);
+    float ca, cb;
+    bn_acc_bwd_channel(a.bw, raw, t0, ca, cb, (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
+    float* cf = (float*)(lds + R16_CF);
+    cf[t0] = ca;
+    cf[16 + t0] = cb;
+    cf[32 + t0] = raw.scale;
+    cf[48 + t0] = a.bw.st[3 * a.bw.CS + t0];
+  }
   f32x4 wacc[TPW];
 #pragma unroll
   for (int j = 0; j < TPW; ++j) wacc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   float imgv[256 / NTHR];
-  u32x4 v[ITER];
+  u32x4 v[POOLDY ? 1 : ITER];
+  u32x4 pv[POOLDY ? 5 : 1];  // POOLDY: the five requests of the thread's first work item
   uint2 ypre[RECOMP ? 1 : MW];
   constexpr int PPT = 256 / NTHR;
   // RECOMP: the filter fragment is requested first of all (unconditional loads, k-group 3 -- all padding -- selects zero below)
@@ -657,13 +696,85 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
     const int voff = (hy0 * a.W + hx0) * 32 + ch * 16;
     const __amdgpu_buffer_rsrc_t rs = rsrc(a.dy + (((long)n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * 32);
 #pragma unroll
-    for (int k = 0; k < ITER; ++k) {
+    for (int k = 0; k < (POOLDY ? 0 : ITER); ++k) {
       bool inb = true;
       if (!interior) {
         const int gy = y0 - 1 + hy0 + RPI * k, gx = x0 - 1 + hx0;
         inb = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
       }
       v[k] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, inb ? voff : OOB, RPI * k * a.W * 32, 0));
+    }
+  };
+  // POOLDY work item of thread t in round rd: item t (rd 0) or 64 + t (rd 1: threads 64 .. 97 -> items 128 .. 161) -> 8-channel
+  // half item & 1 of window item >> 1 = (wy, wx) of the 9 x 9, first pixel (y0 - 2 + 2 wy, x0 - 2 + 2 wx); `in`: a real
+  // item whose window lies inside the image (whole windows: H, W even)
+  auto pool_item = [&](const int t, const int rd, int& half, int& wy, int& wx) {
+    const int item = rd ? t + 64 : t;
+    half = item & 1;
+    const int w = item >> 1;
+    wy = w / 9;
+    wx = w - 9 * wy;
+    bool in = item < 162;
+    if (!interior) {
+      const int gy = y0 - 2 + 2 * wy, gx = x0 - 2 + 2 * wx;
+      in = in && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+    }
+    return in;
+  };
+  // its five requests: y at the window's four pixels (scan order), then dpool; a lane without a real window inside the image
+  // asks beyond num_records: zeros, no memory touched
+  auto issue_pool = [&](const int n, const int rd, u32x4* r) {
+    int t = t0;
+    asm volatile("" : "+v"(t));
+    int half, wy, wx;
+    const bool in = pool_item(t, rd, half, wy, wx);
+    const int HP = a.H >> 1, WP = a.W >> 1;
+    const __amdgpu_buffer_rsrc_t ry = rsrc(a.yb + (((long)n * a.H + (y0 - 2)) * a.W + (x0 - 2)) * 32);
+    const __amdgpu_buffer_rsrc_t rp = rsrc(a.dpool + (((long)n * HP + ((y0 - 2) >> 1)) * WP + ((x0 - 2) >> 1)) * 32);
+    const int vy = in ? (2 * wy * a.W + 2 * wx) * 32 + half * 16 : OOB;
+    const int vp = in ? (wy * WP + wx) * 32 + half * 16 : OOB;
+    r[0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, vy, 0, 0));
+    r[1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, vy + 32, 0, 0));
+    r[2] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, vy, a.W * 32, 0));
+    r[3] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, vy + 32, a.W * 32, 0));
+    r[4] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rp, vp, 0, 0));
+  };
+  // ... -> dy of the window's pixels that lie in the 16 x 16 halo -> LDS (the dy halo's layout)
+  auto stage_pool = [&](const int rd, const u32x4* r) {
+    int t = t0;
+    asm volatile("" : "+v"(t));
+    int half, wy, wx;
+    const bool in = pool_item(t, rd, half, wy, wx);
+    const float* cf = (const float*)(lds + R16_CF) + half * 8;
+    float cA[8], cB[8], sc[8], sh[8];
+#pragma unroll
+    for (int q = 0; q < 8; q += 4) {
+      *(f32x4*)&cA[q] = *(const f32x4*)(cf + q);
+      *(f32x4*)&cB[q] = *(const f32x4*)(cf + 16 + q);
+      *(f32x4*)&sc[q] = *(const f32x4*)(cf + 32 + q);
+      *(f32x4*)&sh[q] = *(const f32x4*)(cf + 48 + q);
+    }
+    u32x4 out[4];
+#pragma unroll
+    for (int wi = 0; wi < 4; ++wi) {
+      float o[4][2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int e = wi * 2 + h;
+        SPCL_POOL_WINDOW_DY(bf16_t, r, r[4], wi, h, sc[e], sh[e], cA[e], cB[e], o)
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) out[k][wi] = Word<bf16_t>::make(o[k]);
+    }
+    if (!interior && !in) {  // the zero padding of the transposed convolution
+#pragma unroll
+      for (int k = 0; k < 4; ++k) out[k] = (u32x4){0u, 0u, 0u, 0u};
+    }
+    const bool real = rd == 0 || t < 98;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int hy = 2 * wy - 1 + (k >> 1), hx = 2 * wx - 1 + (k & 1);
+      if (real && hy >= 0 && hy < HW_ && hx >= 0 && hx < HW_) *(u32x4*)(lds + R16_DY + (hy * RP + hx) * PS + half * 16) = out[k];
     }
   };
   // y2 at the wave's rows: ONE lane offset (pixel column r16 -- 13 for the two unused columns -- and channel quarter g),
@@ -686,7 +797,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
   if (stamp) tc = __builtin_amdgcn_s_memtime();
   if (n_first < a.N) {
     issue_img(n_first);
-    issue_halo(n_first);
+    if (POOLDY) issue_pool(n_first, 0, pv);
+    else issue_halo(n_first);
     if (!RECOMP) issue_y2(n_first);
   }
   uint2 wfp = {0u, 0u};  // the A fragment (s16x4) as two registers
@@ -781,6 +893,21 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
     const int lane = t & 63, r16 = t & 15, g = lane >> 4;
     // the filter fragments (5 KB, L1-resident) are requested again for every tile -- behind the tile's own requests issued a
     // tile period ago, used after everything older: twenty registers that are free outside the dgrad rows
+    if (POOLDY) {
+      // dy of the tile's halo -> LDS, FIRST: the work items' registers (20 requested + 32 coefficients + 16 results) and the
+      // 32 of the filter fragments and coefficients requested below do not fit side by side (scratch).  Wave 1's second item
+      // is requested behind its first: twenty more registers in flight across the first spilled too
+      __builtin_amdgcn_sched_barrier(0);
+      stage_pool(0, pv);
+      __builtin_amdgcn_sched_barrier(0);
+      if (wave == 1) {
+        u32x4 pw[5];
+        issue_pool(n, 1, pw);
+        __builtin_amdgcn_sched_barrier(0);
+        stage_pool(1, pw);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
     u32x4 wall[NSTEPS];
 #pragma unroll
     for (int s = 0; s < NSTEPS; ++s)
@@ -811,7 +938,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
         if (hc + e >= 2) imb[512 - 2] = hb;
       }
     }
-    {
+    if (!POOLDY) {
       const int ch = t & 1, q0 = t >> 1, hy0 = q0 / HW_, hx0 = q0 % HW_;
       unsigned char* const lp = lds + R16_DY + (hy0 * RP + hx0) * PS + ch * 16;
 #pragma unroll
@@ -903,7 +1030,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(r16_wpe(SHI
       }
     }
     if (!(it + 1 < a.ipw && n + 1 < a.N)) break;
-    issue_halo(n + 1);
+    if (POOLDY) issue_pool(n + 1, 0, pv);
+    else issue_halo(n + 1);
     if (!RECOMP) issue_y2(n + 1);
     issue_img(n + 1);
     second_half(n);
@@ -984,13 +1112,21 @@ extern "C" int spcl_conv16_bwd_fused_splits(int N, int H, int W) {
   return cdiv(H, B16_TH) * cdiv(W, B16_TW) * cdiv(N, ipw);
 }
 
+// the pooled form's extra inputs (spcl_conv16_bwd_fused_image_pooled): dy == null, formed from these in the kernel's loader
+struct Bwd16Pooled {
+  const void* y;       // [N][H][W][16] bf16, this convolution's raw output
+  const void* dpool;   // [N][H/2][W/2][16] bf16
+  BnAccBwd bw;         // its BatchNorm's backward block, forward coefficients and gradient outputs
+};
+
 // y2 == null: the first conv's output was never stored (spcl_conv16_bwd_fused_image): w_packed_image, whole tiles of any size
+// pooled != null (with y2 == null): dy is not stored either
 static int conv16_bwd_fused_impl(const void* dy, int dtype, int N, int H, int W, const void* w_packed_dgrad,
                                  const void* y2, const void* w_packed_image, const float* scale2, const float* shift2,
                                  const float* mean2, const float* image, float* rows11, float* partial, float* dw_oihw,
                                  int Cin, int Cout, float* wg_rows, const float* acorr, int nacorr, float* acorr16,
-                                 void* stream) {
-  SPCL_CHECK_ARG(dy && w_packed_dgrad && (y2 || w_packed_image) && scale2 && shift2 && mean2 && image && partial && dw_oihw,
+                                 void* stream, const Bwd16Pooled* pooled = nullptr) {
+  SPCL_CHECK_ARG((dy != nullptr) != (pooled != nullptr) && w_packed_dgrad && (y2 || w_packed_image) && scale2 && shift2 && mean2 && image && partial && dw_oihw,
                  "conv16_bwd_fused: null pointer");
   SPCL_CHECK_ARG((rows11 != nullptr) != (wg_rows != nullptr), "conv16_bwd_fused: exactly one of rows11 / wg_rows");
   SPCL_CHECK_ARG(wg_rows == nullptr || (acorr && acorr16 && nacorr > 0), "conv16_bwd_fused: wg_rows comes with the autocorrelation rows");
@@ -1014,6 +1150,10 @@ static int conv16_bwd_fused_impl(const void* dy, int dtype, int N, int H, int W,
   a.wp_img = (const u32x4*)w_packed_image;
   a.scale2 = scale2; a.shift2 = shift2; a.mean2 = mean2; a.img = image; a.rows11 = rows11; a.partial = partial;
   a.wg_rows = wg_rows; a.acorr_in = acorr; a.nacorr = nacorr; a.acorr_out = acorr16;
+  a.yb = nullptr; a.dpool = nullptr; a.bw = BnAccBwd{};
+  if (pooled != nullptr) {
+    a.yb = (const unsigned char*)pooled->y; a.dpool = (const unsigned char*)pooled->dpool; a.bw = pooled->bw;
+  }
   a.N = N; a.H = H; a.W = W; a.tilesX = cdiv(W, B16_TW); a.tilesY = cdiv(H, B16_TH);
   a.ipw = conv16_bwd_ipw(N, H, W);
   static const int env_remap = lab_env("SPCL_CONV_XCD_REMAP", 1);
@@ -1022,7 +1162,8 @@ static int conv16_bwd_fused_impl(const void* dy, int dtype, int N, int H, int W,
   const int nz = cdiv(N, a.ipw), nsplit = a.tilesX * a.tilesY * nz;
   a.nwg = nsplit;
   const double px = (double)N * H * W;
-  prof_cost(px * 32.0 * (y2 != nullptr ? 2.0 : 1.0) + px * 4.0 + (double)nsplit * 9 * 256 * 4.0, 2.0 * px * 9.0 * 256 * 2.0 + 2.0 * px * 9.0 * 16);
+  // bytes: dy (pooled: y and dpool, a quarter of it, in its place) + y2 where it is stored + the image + the slabs
+  prof_cost(px * 32.0 * ((pooled != nullptr ? 1.25 : 1.0) + (y2 != nullptr ? 1.0 : 0.0)) + px * 4.0 + (double)nsplit * 9 * 256 * 4.0, 2.0 * px * 9.0 * 256 * 2.0 + 2.0 * px * 9.0 * 16);
   a.stamps = nullptr;
   const bool want_stamps = SPCL_CONV16_STAMPS_BUILD && lab_flag("SPCL_CONV16_STAMPS");  // debug only (synchronises)
   const size_t nwg = (size_t)nsplit;
@@ -1041,7 +1182,10 @@ static int conv16_bwd_fused_impl(const void* dy, int dtype, int N, int H, int W,
     else if (wgr) B16_LAUNCH(true, NW_, true);              \
     else B16_LAUNCH(true, NW_, false);                      \
   }
-  if (y2 == nullptr) {  // (spcl_conv16_bwd_fused_image_supported: the row-mapped kernel on whole tiles)
+  if (pooled != nullptr) {  // (spcl_conv16_bwd_fused_image_pooled_supported: ... and dy from y and dpool)
+    if (wgr) SPCL_LAUNCH((conv16_bwd_rows_kernel<false, true, true, true>), grid, dim3(128), B16_LDS_POOLDY, st, a);
+    else SPCL_LAUNCH((conv16_bwd_rows_kernel<false, false, true, true>), grid, dim3(128), B16_LDS_POOLDY, st, a);
+  } else if (y2 == nullptr) {  // (spcl_conv16_bwd_fused_image_supported: the row-mapped kernel on whole tiles)
     if (wgr) SPCL_LAUNCH((conv16_bwd_rows_kernel<false, true, true>), grid, dim3(128), B16_LDS_ROWS, st, a);
     else SPCL_LAUNCH((conv16_bwd_rows_kernel<false, false, true>), grid, dim3(128), B16_LDS_ROWS, st, a);
   } else if (nw == 2 && conv16_bwd_rowmap()) {
@@ -1109,4 +1253,36 @@ extern "C" int spcl_conv16_bwd_fused_image(const void* dy, int dtype, int N, int
   SPCL_CHECK_ARG(w_packed_image != nullptr, "conv16_bwd_fused_image: null pointer");
   return conv16_bwd_fused_impl(dy, dtype, N, H, W, w_packed_dgrad, nullptr, w_packed_image, scale2, shift2, mean2, image, rows11,
                                partial, dw_oihw, Cin, Cout, wg_rows, acorr, nacorr, acorr16, stream);
+}
+
+// spcl_conv16_bwd_fused_image whose incoming gradient is never materialised (unet.py:75-77, 118-121 and autograd: the block's
+// output goes through BatchNorm + ReLU + the 2 x 2 max-pool only): instead of dy the call takes what spcl_bnrelu_backward_rows_acc
+// formed it from -- y (this convolution's raw output), dpool, the per-tile rows of the BatchNorm's backward sums and its zeroed
+// accumulator block -- adds the rows to the block (that call's small launch, unchanged) and the one-pass kernel forms dy per
+// tile in its loader, bit for bit what the apply pass wrote.  dgamma / dbeta of that BatchNorm are written by the kernel's
+// first workgroup.  Two launches for three; the 103 MB dy at 64 x 224^2 is neither written nor read.
+extern "C" int spcl_conv16_bwd_fused_image_pooled_supported(int dtype, int N, int H, int W, int CinK, int CoutS, int training) {
+  return (training != 0 && spcl_conv16_bwd_fused_image_supported(dtype, N, H, W, CinK, CoutS)) ? 1 : 0;
+}
+
+extern "C" int spcl_conv16_bwd_fused_image_pooled(const void* y, const void* dpool, const float* rows, int nrows, int dtype, int N,
+                                                  int H, int W, const float* st4, int training, long long* acc, float* dgamma,
+                                                  float* dbeta, const void* w_packed_dgrad, const void* w_packed_image,
+                                                  const float* scale2, const float* shift2, const float* mean2,
+                                                  const float* image, float* rows11, float* partial, float* dw_oihw, int Cin,
+                                                  int Cout, float* wg_rows, const float* acorr, int nacorr, float* acorr16,
+                                                  void* stream) {
+  SPCL_CHECK_ARG(y && dpool && rows && nrows > 0 && st4 && acc && dgamma && dbeta && w_packed_image,
+                 "conv16_bwd_fused_image_pooled: null pointer");
+  if (!spcl_conv16_bwd_fused_image_pooled_supported(dtype, N, H, W, 16, 16, training)) {
+    set_error("conv16_bwd_fused_image_pooled: unsupported configuration (training, bf16, 16 -> 16 channels, H and W multiples "
+              "of 14, the row-mapped kernel)");
+    return SPCL_EUNSUPPORTED;
+  }
+  launch_bwd_rows_acc(rows, nrows, 16, acc, (hipStream_t)stream);
+  Bwd16Pooled p;
+  p.y = y; p.dpool = dpool;
+  p.bw = BnAccBwd{acc, st4, dgamma, dbeta, (float)((size_t)N * H * W), training, 16, 16};
+  return conv16_bwd_fused_impl(nullptr, dtype, N, H, W, w_packed_dgrad, nullptr, w_packed_image, scale2, shift2, mean2, image, rows11,
+                               partial, dw_oihw, Cin, Cout, wg_rows, acorr, nacorr, acorr16, stream, &p);
 }

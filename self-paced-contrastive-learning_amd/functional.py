@@ -1131,6 +1131,10 @@ def _conv_image_acorr(x_store, dt_code, dtype, N, H, W, cin_s, cout_s, wp, want_
 # A/B switch: 0 = the image block stores its first convolution's raw output (103 MB at 64 x 224^2: written once, read by the
 # second convolution's forward and by its backward) instead of forming it again per tile from the image in those two launches
 _BLOCK1_RECOMPUTE = os.environ.get("SPCL_BLOCK1_RECOMPUTE", "1") != "0"
+# A/B switch: 0 = the image block's backward materialises the gradient behind Conv1.b's BatchNorm + ReLU + max-pool (103 MB at
+# 64 x 224^2: written by the BatchNorm apply pass, read back once by the one-pass backward of Conv1.b, its only reader) instead
+# of that kernel forming it per tile from Conv1.b's raw output and the pooled gradient (spcl_conv16_bwd_fused_image_pooled)
+_BLOCK1_POOLED_BWD = os.environ.get("SPCL_BLOCK1_POOLED_BWD", "1") != "0"
 
 
 def _conv_from_image(image, y_image, dt_code, dtype, N, H, W, cout_s, wp_image, scale, shift, wp, want_stats):
@@ -1597,16 +1601,21 @@ _CONV16_FUSED = os.environ.get("SPCL_CONV16_FUSED", "1") != "0"  # A/B switch: 0
 _CONV16_WGROWS = os.environ.get("SPCL_CONV16_WGROWS", "1") != "0"  # A/B switch: 0 = per-tile rows + the folding launch
 
 
-def _conv16_bwd_fused(dy, wp_t, y2, st2, image, dt_code, N, H, W, cin, cout, cs, sink, acorr=None, wp_image=None):
+def _conv16_bwd_fused(dy, wp_t, y2, st2, image, dt_code, N, H, W, cin, cout, cs, sink, acorr=None, wp_image=None, pooled=None):
     """the image block's second conv, whole backward in one launch (csrc/conv16_bwd.hip): -> (dW or None when it went into
     a bucket slice, rows of the first conv's BatchNorm backward / weight gradient).  With ``acorr`` (the autocorrelation's
     partial rows) the rows come as ONE set per workgroup in the final kernel's layout (``rows.wg``) and the same launch
     folds ``acorr`` to 16 rows (``rows.acorr16``): no per-tile rows, no folding launch; else per tile ([tiles][11][cs]).
     ``y2`` None: the first conv's output was never stored -- the kernel forms it from ``image`` and ``wp_image``, that conv's
-    packed forward weights (spcl_conv16_bwd_fused_image)."""
-    dev = dy.device
+    packed forward weights (spcl_conv16_bwd_fused_image).  ``pooled`` (with ``dy`` and ``y2`` None): ``dy`` was never stored
+    either -- (y, dpool, rows, st, acc, dgamma, dbeta, training) of this convolution's BatchNorm + ReLU + max-pool, from which
+    the kernel's loader forms it (spcl_conv16_bwd_fused_image_pooled, which also adds ``rows`` to the zeroed block ``acc`` and
+    leaves dgamma / dbeta)."""
+    dev = image.device
     if y2 is None and wp_image is None:
         raise RuntimeError("conv16 backward: neither the first convolution's output nor its packed weights")
+    if (dy is None) != (pooled is not None) or (pooled is not None and y2 is not None):
+        raise RuntimeError("conv16 backward: exactly one of the gradient and the tensors it is formed from")
     nsplit = _n.call("spcl_conv16_bwd_fused_splits", N, H, W)
     if acorr is not None:
         rows = torch.empty(11 * cs * nsplit, dtype=torch.float32, device=dev)
@@ -1619,6 +1628,14 @@ def _conv16_bwd_fused(dy, wp_t, y2, st2, image, dt_code, N, H, W, cin, cout, cs,
     dw = _grad_buffer(sink, (cout, cin, 3, 3), dev)
 
     def launch():
+        if pooled is not None:
+            yb, dpool, prow, stb, acc, dgamma, dbeta, training = pooled
+            _n.call("spcl_conv16_bwd_fused_image_pooled", _n.ptr(yb), _n.ptr(dpool), _n.ptr(prow), prow.ntiles, dt_code, N, H, W,
+                    _n.ptr(stb), int(training), _n.ptr(acc), _n.ptr(dgamma), _n.ptr(dbeta), _n.ptr(wp_t), _n.ptr(wp_image),
+                    _n.ptr(st2[2]), _n.ptr(st2[3]), _n.ptr(st2[0]), _n.ptr(image), _n.ptr(rows) if not rows.wg else None,
+                    _n.ptr(ws), _n.ptr(dw), cin, cout, _n.ptr(rows) if rows.wg else None, _n.ptr(acorr),
+                    0 if acorr is None else acorr.shape[0], _n.ptr(rows.acorr16) if rows.wg else None, _n.stream())
+            return
         _n.call("spcl_conv16_bwd_fused" if y2 is not None else "spcl_conv16_bwd_fused_image", _n.ptr(dy), dt_code, N, H, W,
                 _n.ptr(wp_t), _n.ptr(y2 if y2 is not None else wp_image), _n.ptr(st2[2]),
                 _n.ptr(st2[3]), _n.ptr(st2[0]), _n.ptr(image), _n.ptr(rows) if not rows.wg else None, _n.ptr(ws), _n.ptr(dw),
@@ -1627,7 +1644,8 @@ def _conv16_bwd_fused(dy, wp_t, y2, st2, image, dt_code, N, H, W, cin, cout, cs,
 
     queue = sink_queue(sink)
     if queue is not None and _TAILS:
-        if queue.capture_tail(sink, (ws, dy, y2, image, rows, wp_image), launch):
+        # (kept alive until the flush; the queue takes its device from element 1: a tensor, never the absent dy)
+        if queue.capture_tail(sink, (ws, image, dy, y2, rows, wp_image, pooled), launch):
             return None, rows
         return dw, rows
     launch()
@@ -1956,6 +1974,7 @@ class _ConvBlockFn(torch.autograd.Function):
         sk = tuple(take_grad_sink(p, ng[i + 1]) for i, p in enumerate(ctx.params))  # (wa, ga, ba, wb, gb, bb)
         lk = cfg.link_out
         la = getattr(cfg, "link_act", None)
+        pooled = None  # (set where dyb is not materialised: ``_BLOCK1_POOLED_BWD``)
         if la is not None and da_s is not None and dp_s is None and da_stride == 0 and la.fresh(da_s.data_ptr()):
             # the consumer's backward (the 1x1 head) left this BatchNorm's partial sums next to the activation gradient
             dyb, dgb, dbb = _bnrelu_bwd_rows(yb, da_s, None, la.rows, dtc, dtype, N, H, W, cout, cout_s, stb, cfg.training,
@@ -1975,7 +1994,20 @@ class _ConvBlockFn(torch.autograd.Function):
                                                 sk[4:6], _take_acc(ctx, "acc_bwd_b"))
             else:
                 acc = _take_acc(ctx, "acc_bwd_b") if (_ACC_FILL and H % 2 == 0 and W % 2 == 0 and cout_s <= 256) else None
-                if acc is not None:  # (the rows go into this block's own, untouched, accumulator block: no finalize launch)
+                if (acc is not None and _BLOCK1_POOLED_BWD and ya is None and ctx.acorr is not None and ctx.wpa_fwd is not None
+                        and ctx.needs_input_grad[4] and cout == cout_s and dtype == torch.bfloat16
+                        and _n.call("spcl_conv16_bwd_fused_image_pooled_supported", dtc, N, H, W, cout_s, cout_s,
+                                    int(cfg.training))):
+                    # the image block with its first convolution recomputed: this gradient's ONE reader is the one-pass
+                    # backward of Conv1.b below, which forms it per tile from yb and the pooled gradient -- no tensor, no
+                    # apply launch; that call adds the rows to the block and leaves dgamma / dbeta
+                    dyb = None
+                    dgb, dbb = _grad_buffer(sk[4], (cout,), yb.device), _grad_buffer(sk[5], (cout,), yb.device)
+                    # (views of their own for the call: ``pooled`` stays alive in the weight-gradient queue until its flush,
+                    # and a gradient somebody else still holds is CLONED by autograd instead of adopted as ``param.grad`` --
+                    # two copies and, the sink then unclaimed, an addition into the bucket per step)
+                    pooled = (yb, dp_s, lk.rows, stb, acc, dgb.view(cout), dbb.view(cout), cfg.training)
+                elif acc is not None:  # (the rows go into this block's own, untouched, accumulator block: no finalize launch)
                     dyb, dgb, dbb = _bnrelu_bwd_rows_acc(yb, None, dp_s, lk.rows, dtc, dtype, N, H, W, cout, cout_s, stb,
                                                          cfg.training, sk[4:6], acc)
                 else:
@@ -2010,9 +2042,12 @@ class _ConvBlockFn(torch.autograd.Function):
         if ya is None and not one_pass:  # (the forward offered the recomputation where this holds: never a silent fallback)
             raise RuntimeError("image block backward: the first convolution's output was not stored and the one-pass kernel "
                                "that forms it again is not available")
+        if pooled is not None and not one_pass:  # (taken only where the one-pass kernel runs: never a silent fallback)
+            raise RuntimeError("image block backward: the gradient behind the max-pool was not materialised and the one-pass "
+                               "kernel that forms it is not available")
         if one_pass:
             dwb, rows16 = _conv16_bwd_fused(dyb, wpb_t, ya, sta, xs, dtc, N, H, W, cout, cout, cout_s, sk[3],
-                                            acorr=ctx.acorr if _CONV16_WGROWS else None, wp_image=ctx.wpa_fwd)
+                                            acorr=ctx.acorr if _CONV16_WGROWS else None, wp_image=ctx.wpa_fwd, pooled=pooled)
         else:
             dwb = _wgrad(ya, dyb, dtc, N, H, W, cout, cout_s, cout_s, cout, cout_s, 1, sta[2], sta[3], sk[3]) \
                 if ctx.needs_input_grad[4] else None

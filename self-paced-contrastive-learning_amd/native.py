@@ -132,6 +132,9 @@ _SIGNATURES = {
     "spcl_conv16_bwd_fused_image_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "spcl_conv16_bwd_fused_image": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int,
                                             _P, _P, c_int, _P, _P]),
+    "spcl_conv16_bwd_fused_image_pooled_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "spcl_conv16_bwd_fused_image_pooled": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P,
+                                                   _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, _P, _P]),
     "spcl_conv16_bwd_fused_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "spcl_conv16_bwd_fused_splits": (c_int, [c_int, c_int, c_int]),
     "spcl_conv16_bwd_fused": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int,
@@ -320,13 +323,14 @@ class WgradTail(ctypes.Structure):
                 ("nblk_co", c_int), ("CIB", c_int), ("COB", c_int), ("Cin", c_int), ("Cout", c_int)]
 
 
-ABI_VERSION = 24  # == SPCL_ABI_VERSION of include/spcl_hip.h (tests/test_abi.py compares them); lib() refuses any other library
+ABI_VERSION = 25  # == SPCL_ABI_VERSION of include/spcl_hip.h (tests/test_abi.py compares them); lib() refuses any other library
 WGRAD_BATCH_MAX = 16
 WGRAD_TAILS_MAX = 16
 _NO_STATUS = ("spcl_abi_version", "spcl_block1_recompute_supported", "spcl_block1_kernels_take", "spcl_conv16_bwd_fused_image_supported", "spcl_conv3x3_forward_image_acorr_rows", "spcl_image_autocorr_rows", "spcl_conv_dgrad_bnstats_image_supported", "spcl_conv16_bwd_fused_supported", "spcl_conv16_bwd_fused_splits", "spcl_conv_num_tiles", "spcl_conv_stat_rows", "spcl_conv_set_gemm", "spcl_conv_set_f32_split", "spcl_conv_get_f32_split", "spcl_supcon_unit_gradient_block", "spcl_conv_cat_supported", "spcl_conv_up2_supported", "spcl_conv_split_supported", "spcl_conv_split_bnstats_supported", "spcl_conv1x1_bwd_rows", "spcl_profile_count", "spcl_conv_dgrad_bnstats_supported", "spcl_conv_dgrad_poolstats_supported",
               "spcl_conv_wgrad_batched_supported", "spcl_conv_bn_acc_supported", "spcl_conv_dgrad_bnstats_acc_supported",
               "spcl_conv_dgrad_poolstats_acc_supported", "spcl_supcon_rows_supported", "spcl_bnrelu_gap_supported",
-              "spcl_conv_dgrad_poolmax_supported", "spcl_conv_dgrad_poolmax_acc_supported")
+              "spcl_conv_dgrad_poolmax_supported", "spcl_conv_dgrad_poolmax_acc_supported",
+              "spcl_conv16_bwd_fused_image_pooled_supported")
 
 
 class NativeLibraryError(RuntimeError):
