@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 25
+#define SPCL_ABI_VERSION 26
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -378,6 +378,16 @@ int spcl_adaptive_pool2d_backward(const float* dout, const int* argmax, int dtyp
  * backward. */
 int spcl_l2norm_rows_forward(const float* x, size_t rows, int O, float* z, void* stream);
 int spcl_l2norm_rows_backward(const float* x, const float* dz, size_t rows, int O, float* dx, void* stream);
+
+/* Normalize() and SoftmaxWithT's division of the cluster heads, on the logits (contrastyou/projectors/heads.py:42-75 with
+ * nn.py:29-36, :50-58 of the reference): over `rows` rows of pitch ld, per subhead s < S,
+ *   z[m][s*K + k] = l[m][s*K + k] / max(||l[m][s*K ..]||_2, 1e-12) / T        (normalize == 0: l / T)
+ * and the exact backward (below 1e-12 the denominator is the constant).  f32, one thread per (row, subhead), no atomics;
+ * columns >= S*K are neither read nor written.  z, dz and dl have the pitch of l.  T > 0. */
+int spcl_group_l2norm_temp_forward(const float* l, size_t rows, long ld, int S, int K, int normalize, float T, float* z,
+                                   void* stream);
+int spcl_group_l2norm_temp_backward(const float* l, const float* dz, size_t rows, long ld, int S, int K, int normalize, float T,
+                                    float* dl, void* stream);
 
 /* The same weight gradients for SEVERAL layers in ONE launch (bf16, channel counts multiples of 64: _Conv3.b.._Conv5.b
  * and the decoder's wide layers).  The workgroups split the union of the layers' pixel ranges, so the launch writes
@@ -1041,6 +1051,30 @@ int spcl_iic_patch_forward(const float* lx, const float* ly, int N, int C, int H
                            void* ws, size_t ws_bytes, void* stream);
 int spcl_iic_patch_backward(const float* lx, const float* ly, int N, int C, int H, int W, int pad, int patch,
                             const uint8_t* flags_y, const float* dj, const float* gscale, float* dlx, float* dly, void* stream);
+
+/* The same criterion over S subheads: the decoder criterion of the IIC estimators (csrc/iic_patch.hip).  Replaces
+ * IICEstimator.forward's decoder branch (semi_seg/mi_estimator/discrete_mi_estimator.py:33-40, :53-60: per subhead
+ * IIDSegmentationSmallPathLoss(padding, patch_size) on the probability maps of a DenseClusterHead, contrastyou/projectors/
+ * heads.py:149-169) as semi_seg/epochers/_mixins.py:86 calls it with Y flipped.
+ * lx / ly: logits [N][H][W][ld] f32, subhead s in columns s*K .. s*K+K-1, ld >= S*K; 2 <= K <= 32, 0 <= pad <= 7, patch >= 2.
+ * flags_y, the patch starts, the clipping and PX = 0 outside the PATCH are those of spcl_iic_patch_*; per (s, P) the joint
+ * and IIDSegmentationLoss (iic_loss.py:77-97, lamda = 1) in float64 from 32.32 fixed-point joints.
+ *   spcl_iic_patch_heads_plan:     argument check without a launch; patch count nP of ONE subhead, workspace bytes, f32
+ *                          elements of dj (each output pointer may be NULL).
+ *   spcl_iic_patch_heads_forward:  loss[0] = scale * sum_s mean_P loss_{s,P}; head_patch_loss (nullable, [S][nP]) = the
+ *                          loss_{s,P}, not scaled; nan_flag[0] = 1 when any of them is NaN; dj = d loss / d J_{s,P} as
+ *                          spcl_iic_patch_heads_backward reads it.  ws is zeroed by the call.  Bitwise deterministic.
+ *   spcl_iic_patch_heads_backward: dlx = d loss / d lx (times *gscale when non-NULL) in columns s*K + k only; dly, when
+ *                          non-NULL, the same for ly at Y's unflipped position.  Each element is written exactly once, no
+ *                          atomics; columns >= S*K are left alone. */
+int spcl_iic_patch_heads_plan(int N, int S, int K, long ld, int H, int W, int pad, int patch, int* num_patches,
+                              size_t* ws_bytes, size_t* dj_elems);
+int spcl_iic_patch_heads_forward(const float* lx, const float* ly, long ld, int N, int H, int W, int S, int K, int pad,
+                                 int patch, const uint8_t* flags_y, float scale, float* loss, float* head_patch_loss,
+                                 int* nan_flag, float* dj, void* ws, size_t ws_bytes, void* stream);
+int spcl_iic_patch_heads_backward(const float* lx, const float* ly, long ld, int N, int H, int W, int S, int K, int pad,
+                                  int patch, const uint8_t* flags_y, const float* dj, const float* gscale, float* dlx,
+                                  float* dly, void* stream);
 
 /* ---------------------------------------------------------------- mean teacher / entropy minimisation (csrc/semi_reg.hip) ----
  * Replaces the arithmetic of semi_seg/hooks/mt.py:48-54 and semi_seg/hooks/entmin.py:30-34 of the reference.

@@ -49,6 +49,7 @@ _MIRRORED = {
     "semi_seg.utils": "semi_seg.utils",
     "semi_seg.mi_estimator": "semi_seg.mi_estimator",
     "semi_seg.mi_estimator.mineestimator": "semi_seg.mi_estimator.mine",
+    "semi_seg.mi_estimator.discrete_mi_estimator": "semi_seg.mi_estimator.discrete_mi_estimator",
     "semi_seg.epochers": "semi_seg.epochers",
     "semi_seg.epochers.new_pretrain": "semi_seg.epochers.pretrain",
     "semi_seg.epochers.new_epocher": "semi_seg.epochers.finetune",

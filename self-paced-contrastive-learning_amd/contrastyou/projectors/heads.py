@@ -109,16 +109,19 @@ def init_dense_sub_header(head_type, input_dim, hidden_dim, num_clusters, normal
 
 
 class _ClusterHeadBase(_ProjectorHeadBase):
-    def _check_fast(self):
-        if self._head_type != "linear" or self._normalize or self._T != 1:
-            raise NotImplementedError(f"{type(self).__name__}: head_type={self._head_type!r}, normalize={self._normalize} "
-                                      "(the UDA-IIC hooks build linear heads without normalisation)")
+    """``logits()`` is what the fused criteria consume: the subheads' outputs after ``Normalize()`` (when ``normalize``) and
+    ``SoftmaxWithT``'s division, before the softmax -- one launch of ``functional.group_l2norm_temp`` behind the product,
+    none when ``normalize`` is off and ``T == 1``."""
+
+    def _temper(self, lg):
+        return F_hip.group_l2norm_temp(lg, num_subheads=len(self._headers), num_clusters=self._output_dim,
+                                       normalize=self._normalize, T=self._T)
 
     def forward(self, features):
         """list of S probability maps, as the reference returns them"""
         lg = self.logits(features)
-        K = lg.shape[1] // len(self._headers)
-        return [(lg[:, s * K:(s + 1) * K] / self._T).softmax(1) for s in range(len(self._headers))]
+        K = self._output_dim
+        return [lg[:, s * K:(s + 1) * K].softmax(1) for s in range(len(self._headers))]
 
 
 class ClusterHead(_ClusterHeadBase):
@@ -133,11 +136,17 @@ class ClusterHead(_ClusterHeadBase):
                             normalize=self._normalize, T=self._T) for _ in range(self._num_subheads)])
 
     def logits(self, features):
-        """[N, S*K, 1, 1] f32 logits of every subhead (pool + one product over the stacked weights: csrc/projector.hip)"""
-        self._check_fast()
+        """[N, S*K, 1, 1] f32 logits of every subhead (pool + one product over the stacked weights: csrc/projector.hip);
+        ``mlp`` subheads: the pooled rows through the stacked first layers, then the S second layers on column slices"""
+        if self._head_type == "mlp":
+            hs = self._headers
+            pooled = F_hip.adaptive_pool2d(features, (1, 1), "avg")
+            return self._temper(F_hip.cluster_mlp_logits(
+                pooled, torch.cat([h[2].weight for h in hs], 0), torch.cat([h[2].bias for h in hs], 0),
+                torch.stack([h[4].weight for h in hs], 0), torch.stack([h[4].bias for h in hs], 0)))
         w = torch.cat([h[2].weight for h in self._headers], 0)
         b = torch.cat([h[2].bias for h in self._headers], 0)
-        out = F_hip.projector(features, w, b, None, None, False)
+        out = self._temper(F_hip.projector(features, w, b, None, None, False))
         return out.view(out.shape[0], out.shape[1], 1, 1)
 
 
@@ -155,8 +164,13 @@ class DenseClusterHead(_ClusterHeadBase):
             for _ in range(num_subheads)])
 
     def logits(self, features):
-        """[N, S*K, H, W] f32 logits (channels-last) of every subhead: one pixel-row product over the stacked weights"""
-        self._check_fast()
+        """[N, S*K, H, W] f32 logits (channels-last) of every subhead: one pixel-row product over the stacked weights; ``mlp``
+        subheads: one product over the stacked first layers, then the S second layers on its column slices"""
+        if self._head_type == "mlp":
+            hs = self._headers
+            return self._temper(F_hip.cluster_mlp_logits(
+                features, torch.cat([h[0].weight for h in hs], 0), torch.cat([h[0].bias for h in hs], 0),
+                torch.stack([h[2].weight.flatten(1) for h in hs], 0), torch.stack([h[2].bias for h in hs], 0)))
         w = torch.cat([h[0].weight for h in self._headers], 0)
         b = torch.cat([h[0].bias for h in self._headers], 0)
-        return F_hip.pixelwise_mlp(features, w, b)
+        return self._temper(F_hip.pixelwise_mlp(features, w, b))

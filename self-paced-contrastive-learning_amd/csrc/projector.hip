@@ -529,6 +529,84 @@ extern "C" int spcl_l2norm_rows_backward(const float* x, const float* dz, size_t
   return SPCL_OK;
 }
 
+// ---- the cluster heads' Normalize() and SoftmaxWithT division on the logits (contrastyou/projectors/heads.py:42-75 of the
+// reference: ``Normalize() if normalize else Identical(), SoftmaxWithT(1, T=T)``; nn.py:29-36 and :50-58): per subhead s of a row
+// z[s*K + k] = l[s*K + k] / max(||l_s||_2, 1e-12) / T (normalize == 0: l / T).  The criteria apply the softmax themselves as they
+// read z.  One thread per (row, subhead), f32, no atomics; columns >= S*K of the [ld]-wide rows are neither read nor written.
+namespace {
+__global__ __launch_bounds__(256) void group_l2norm_temp_fwd_kernel(const float* __restrict__ l, size_t total, long ld, int S,
+                                                                    int K, int normalize, float T, float* __restrict__ z) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const size_t m = idx / S;
+  const size_t off = m * (size_t)ld + (idx - m * S) * (size_t)K;
+  float d = 1.f;
+  if (normalize) {
+    float ss = 0.f;
+    for (int k = 0; k < K; ++k) ss = fmaf(l[off + k], l[off + k], ss);
+    d = fmaxf(sqrtf(ss), 1e-12f);
+  }
+  for (int k = 0; k < K; ++k) z[off + k] = l[off + k] / d / T;
+}
+
+// g = dz / T;  ||l|| >= eps: dl = (g - u (u . g)) / ||l||, u = l / ||l||;  below eps the denominator is the constant eps
+__global__ __launch_bounds__(256) void group_l2norm_temp_bwd_kernel(const float* __restrict__ l, const float* __restrict__ dz,
+                                                                    size_t total, long ld, int S, int K, int normalize, float T,
+                                                                    float* __restrict__ dl) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const size_t m = idx / S;
+  const size_t off = m * (size_t)ld + (idx - m * S) * (size_t)K;
+  if (!normalize) {
+    for (int k = 0; k < K; ++k) dl[off + k] = dz[off + k] / T;
+    return;
+  }
+  float ss = 0.f, dot = 0.f;
+  for (int k = 0; k < K; ++k) {
+    ss = fmaf(l[off + k], l[off + k], ss);
+    dot = fmaf(l[off + k], dz[off + k] / T, dot);
+  }
+  const float nrm = sqrtf(ss);
+  if (nrm >= 1e-12f) {
+    const float ud = dot / nrm;  // u . g
+    for (int k = 0; k < K; ++k) dl[off + k] = (dz[off + k] / T - l[off + k] / nrm * ud) / nrm;
+  } else {
+    for (int k = 0; k < K; ++k) dl[off + k] = dz[off + k] / T / 1e-12f;
+  }
+}
+
+int group_l2norm_check(const char* name, size_t rows, long ld, int S, int K, float T) {
+  SPCL_CHECK_ARG(rows > 0 && S > 0 && K > 0, "%s: empty input", name);
+  SPCL_CHECK_ARG(ld >= (long)S * K, "%s: row pitch ld = %ld < S * K = %d", name, ld, S * K);
+  SPCL_CHECK_ARG(T > 0.f, "%s: temperature %g is not positive", name, (double)T);
+  SPCL_CHECK_ARG((double)rows * S < 2147483648.0 * 256.0, "%s: too many rows", name);
+  return SPCL_OK;
+}
+}  // namespace
+
+extern "C" int spcl_group_l2norm_temp_forward(const float* l, size_t rows, long ld, int S, int K, int normalize, float T,
+                                              float* z, void* stream) {
+  if (int rc = group_l2norm_check("spcl_group_l2norm_temp_forward", rows, ld, S, K, T)) return rc;
+  SPCL_CHECK_ARG(l && z, "spcl_group_l2norm_temp_forward: null pointer");
+  if (!normalize && T == 1.f && z == l) return SPCL_OK;  // the identity in place: no launch
+  const size_t total = rows * (size_t)S;
+  SPCL_LAUNCH(group_l2norm_temp_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, l, total, ld,
+              S, K, normalize, T, z);
+  SPCL_LAUNCH_CHECK("group_l2norm_temp_fwd_kernel");
+  return SPCL_OK;
+}
+
+extern "C" int spcl_group_l2norm_temp_backward(const float* l, const float* dz, size_t rows, long ld, int S, int K, int normalize,
+                                               float T, float* dl, void* stream) {
+  if (int rc = group_l2norm_check("spcl_group_l2norm_temp_backward", rows, ld, S, K, T)) return rc;
+  SPCL_CHECK_ARG(l && dz && dl, "spcl_group_l2norm_temp_backward: null pointer");
+  const size_t total = rows * (size_t)S;
+  SPCL_LAUNCH(group_l2norm_temp_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, l, dz, total,
+              ld, S, K, normalize, T, dl);
+  SPCL_LAUNCH_CHECK("group_l2norm_temp_bwd_kernel");
+  return SPCL_OK;
+}
+
 // K heads of one shape on the same feature: average pool once, then one launch per layer for all heads
 static int proj_heads_forward(int K, const void* feat, int dtype, int N, int HW, int C, int Cs, const float* const* w1,
                               const float* const* b1, const float* const* w2, const float* const* b2, int hid, int out_dim,

@@ -790,6 +790,85 @@ class _PixelMlpPooledFn(torch.autograd.Function):
         return gfeat, dw1.view(ctx.params[0].shape), db1, dw2.view(ctx.params[2].shape), db2, None
 
 
+class _GroupedLeakyLinearFn(torch.autograd.Function):
+    """The second layers of S ``mlp`` cluster subheads on the column slices of their stacked pre-activation: ``out[:, s*K + k]
+    = b2[s][k] + sum_h W2[s][k][h] LeakyReLU(pre[:, s*Hd + h])``.  S calls of the rows product (csrc/rows_mlp.hip), each reading
+    its slice of ``pre`` through the row pitch with the activation applied as it is read; no block-diagonal weight is built.
+    Backward: per subhead the weight gradient (same pitch and activation) and the unmasked input gradient written into its slice
+    through the output pitch, then one pass applies LeakyReLU' to the whole [M, S*Hd] gradient.  The rows product takes output
+    counts that are multiples of 4: another K is padded with zero rows (and zero gradient columns), forward and backward."""
+
+    @staticmethod
+    def forward(ctx, pre, w2, b2):
+        _n.require_gpu(pre, w2, b2)
+        ps = _class_map_storage(pre.detach())
+        N, H, W, ld = ps.shape
+        S, K, hid = w2.shape
+        M, dev, f32 = N * H * W, ps.device, _n.dtype_code(torch.float32)
+        if ld != S * hid or hid % 4:
+            raise ValueError(f"grouped second layers: {S} subheads of {hid} hidden units (a multiple of 4) on {ld} columns")
+        w2c, b2c = w2.detach().contiguous().float(), b2.detach().contiguous().float()
+        Kp = (K + 3) // 4 * 4  # (the rows product takes output counts that are multiples of 4: zero rows behind K)
+        wp, bp = w2c, b2c
+        if Kp != K:
+            wp, bp = w2c.new_zeros(S, Kp, hid), b2c.new_zeros(S, Kp)
+            wp[:, :K], bp[:, :K] = w2c, b2c
+        out = torch.empty(M, S * K, dtype=torch.float32, device=dev)
+        ys = torch.empty(M, Kp, dtype=torch.float32, device=dev)
+        for s in range(S):
+            _n.call("spcl_rows_linear_forward", ctypes.c_void_p(ps.data_ptr() + 4 * s * hid), f32, ld, 1, _n.ptr(wp[s]),
+                    _n.ptr(bp[s]), M, hid, Kp, _n.ptr(ys), _n.stream())
+            out[:, s * K:(s + 1) * K] = ys[:, :K]
+        ctx.save_for_backward(ps, w2c)
+        ctx.params = (w2, b2)
+        return out.view(N, H, W, S * K).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dout):
+        ps, w2c = ctx.saved_tensors
+        N, H, W, ld = ps.shape
+        S, K, hid = w2c.shape
+        M, dev, f32 = N * H * W, ps.device, _n.dtype_code(torch.float32)
+        Kp = (K + 3) // 4 * 4
+        g = _class_map_storage(dout.detach()).view(M, S * K)
+        ng = ctx.needs_input_grad
+        sk = tuple(take_grad_sink(p, ng[i + 1]) for i, p in enumerate(ctx.params))
+        dw2, db2 = _grad_buffer(sk[0], (S, K, hid), dev), _grad_buffer(sk[1], (S, K), dev)
+        gs = torch.zeros(M, Kp, dtype=torch.float32, device=dev)
+        wp = torch.zeros(Kp, hid, dtype=torch.float32, device=dev)
+        dwp, dbp = torch.empty(Kp, hid, dtype=torch.float32, device=dev), torch.empty(Kp, dtype=torch.float32, device=dev)
+        dact = torch.empty(M, ld, dtype=torch.float32, device=dev)
+        ws = torch.empty(_n.call("spcl_rows_linear_backward_weight_workspace_bytes", M, Kp, hid) // 4 + 1, dtype=torch.float32,
+                         device=dev)
+        for s in range(S):
+            gs[:, :K] = g[:, s * K:(s + 1) * K]
+            wp[:K] = w2c[s]
+            slice_ptr = ctypes.c_void_p(ps.data_ptr() + 4 * s * hid)
+            _n.call("spcl_rows_linear_backward_weight", _n.ptr(gs), f32, slice_ptr, f32, ld, 1, M, Kp, hid, _n.ptr(ws),
+                    ws.numel() * 4, _n.ptr(dwp), _n.ptr(dbp), _n.stream())
+            dw2[s] = dwp[:K]
+            db2[s] = dbp[:K]
+            _n.call("spcl_rows_linear_backward_input", _n.ptr(gs), f32, _n.ptr(wp), None, M, Kp, hid,
+                    ctypes.c_void_p(dact.data_ptr() + 4 * s * hid), f32, ld, _n.stream())
+        dpre = None
+        if ng[0]:
+            # LeakyReLU'(pre) on every row at once: the masked un-pooling with one pixel a window is the identity times the mask
+            dpre = torch.empty_like(ps)
+            _n.call("spcl_adaptive_avgpool2d_backward_act", _n.ptr(dact), _n.ptr(ps), f32, M, 1, 1, ld, 1, 1, _n.ptr(dpre),
+                    _n.stream())
+            dpre = dpre.permute(0, 3, 1, 2)
+        return dpre, dw2, db2
+
+
+def cluster_mlp_logits(feat, w1, b1, w2, b2):
+    """the logits of S ``mlp`` cluster subheads on a logical [N, C, H, W] map (contrastyou/projectors/heads.py:42-75 without
+    the pooling, ``Normalize`` and softmax): ``w1`` [S*Hd, C(,1,1)] / ``b1`` [S*Hd] the stacked first layers -- one product --,
+    LeakyReLU(0.01), ``w2`` [S, K, Hd] / ``b2`` [S, K] the second layers (``_GroupedLeakyLinearFn``) -> f32 logical
+    [N, S*K, H, W]"""
+    pre = pixelwise_mlp(feat, w1.reshape(w1.shape[0], -1, 1, 1), b1)
+    return _GroupedLeakyLinearFn.apply(pre, w2, b2)
+
+
 def pixelwise_mlp_pooled_supported(feat, w1, w2) -> bool:
     return bool(feat.is_cuda and w2 is not None and feat.shape[1] % 4 == 0 and w1.shape[0] % 4 == 0 and w2.shape[0] % 4 == 0)
 
@@ -3050,6 +3129,99 @@ def iic_patch_loss(lx, ly, *, padding, patch_size, scale=1.0, flags=None, out=No
     logits (iic_loss.py:103-128); differentiable w.r.t. ``lx``, and w.r.t. ``ly`` when it requires grad.  ``flags`` flip Y.
     ``out`` (a list) receives (per-patch losses [nP], not scaled; nan flag int32 [1])."""
     return _IICPatchLossFn.apply(lx, ly, flags, int(padding), int(patch_size), float(scale), [] if out is None else out)
+
+
+class _IICPatchHeadsLossFn(torch.autograd.Function):
+    """``scale * sum_s mean_P IIDSegmentationLoss(softmax(lx_s), softmax(flip(ly)_s))`` over the S subheads of two logit maps
+    (the decoder criterion of ``IICEstimator``): the launches of ``_IICPatchLossFn`` with the subhead as a grid axis.
+    ``lx`` / ``ly``: logical [N, ld, H, W] f32 logits, ld >= S*K, subhead s in channels s*K .. s*K+K-1; the channels beyond
+    S*K get a zero gradient.  ``out`` receives (losses f32 [S, nP], nan flag int32 [1])."""
+
+    @staticmethod
+    def forward(ctx, lx, ly, flags, S, K, pad, patch, scale, out):
+        _n.require_gpu(lx, ly)
+        xs, ys = _class_map_storage(lx.detach()), _class_map_storage(ly.detach())
+        if xs.shape != ys.shape:
+            raise AssertionError(f"logit maps {tuple(xs.shape)} / {tuple(ys.shape)} differ")
+        N, H, W, ld = xs.shape
+        dev = xs.device
+        n_patches, ws_bytes, dj_elems = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _n.call("spcl_iic_patch_heads_plan", N, S, K, ld, H, W, pad, patch, ctypes.byref(n_patches), ctypes.byref(ws_bytes),
+                ctypes.byref(dj_elems))
+        nP = len(iic_patch_starts(H, patch)) * len(iic_patch_starts(W, patch))
+        assert nP == n_patches.value, (nP, n_patches.value)
+        fl = _flip_flags_arg(flags, N, dev)
+        ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device=dev)
+        dj = torch.empty(dj_elems.value, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        per_patch = torch.empty(S, nP, dtype=torch.float32, device=dev)
+        flag = torch.empty(1, dtype=torch.int32, device=dev)
+        _n.call("spcl_iic_patch_heads_forward", _n.ptr(xs), _n.ptr(ys), ld, N, H, W, S, K, pad, patch, _n.ptr(fl), c_float(scale),
+                _n.ptr(loss), _n.ptr(per_patch), _n.ptr(flag), _n.ptr(dj), _n.ptr(ws), ws.numel(), _n.stream())
+        out.extend([per_patch, flag])
+        ctx.save_for_backward(xs, ys, dj, fl)
+        ctx.meta = (S, K, pad, patch)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        xs, ys, dj, fl = ctx.saved_tensors
+        S, K, pad, patch = ctx.meta
+        N, H, W, ld = xs.shape
+        gs = None if is_unit_gradient(g) else g.detach().float().reshape(1).contiguous()
+        alloc = torch.empty_like if ld == S * K else torch.zeros_like  # (the launch leaves the channels beyond S*K alone)
+        dlx = alloc(xs)
+        dly = alloc(ys) if ctx.needs_input_grad[1] else None
+        _n.call("spcl_iic_patch_heads_backward", _n.ptr(xs), _n.ptr(ys), ld, N, H, W, S, K, pad, patch, _n.ptr(fl), _n.ptr(dj),
+                _n.ptr(gs), _n.ptr(dlx), _n.ptr(dly), _n.stream())
+        return (dlx.permute(0, 3, 1, 2), None if dly is None else dly.permute(0, 3, 1, 2), None, None, None, None, None, None,
+                None)
+
+
+def iic_patch_heads_loss(lx, ly, *, num_subheads, num_clusters, padding, patch_size, scale=1.0, flags=None, out=None):
+    """``scale * sum_s IIDSegmentationSmallPathLoss(padding, patch_size)(softmax(lx_s), softmax(flip(ly)_s))`` of logical
+    [N, >= S*K, H, W] logits with K <= 32 clusters a subhead (discrete_mi_estimator.py:53-60 sums the same terms and divides by
+    S: pass ``scale = 1 / S``); differentiable w.r.t. ``lx``, and w.r.t. ``ly`` when it requires grad.  ``flags`` flip Y.
+    ``out`` (a list) receives (losses [S, nP], not scaled; nan flag int32 [1])."""
+    return _IICPatchHeadsLossFn.apply(lx, ly, flags, int(num_subheads), int(num_clusters), int(padding), int(patch_size),
+                                      float(scale), [] if out is None else out)
+
+
+class _GroupL2NormTempFn(torch.autograd.Function):
+    """``Normalize()`` and ``SoftmaxWithT``'s division of the cluster heads on [rows, ld] f32 logits (a [N, ld, H, W] map is
+    its N*H*W channels-last rows): per subhead ``l / max(||l_s||, 1e-12) / T`` (csrc/projector.hip)"""
+
+    @staticmethod
+    def forward(ctx, x, S, K, normalize, T):
+        _n.require_gpu(x)
+        xs = _class_map_storage(x.detach()) if x.dim() == 4 else x.detach().contiguous().float()
+        ld = xs.shape[-1]
+        rows = xs.numel() // ld
+        z = torch.empty_like(xs) if ld == S * K else torch.zeros_like(xs)
+        _n.call("spcl_group_l2norm_temp_forward", _n.ptr(xs), rows, ld, S, K, int(normalize), c_float(T), _n.ptr(z), _n.stream())
+        ctx.save_for_backward(xs)
+        ctx.meta = (S, K, int(normalize), T, x.dim())
+        return z.permute(0, 3, 1, 2) if x.dim() == 4 else z
+
+    @staticmethod
+    def backward(ctx, dz):
+        (xs,) = ctx.saved_tensors
+        S, K, normalize, T, dim = ctx.meta
+        ld = xs.shape[-1]
+        rows = xs.numel() // ld
+        dzs = _class_map_storage(dz.detach()) if dim == 4 else dz.detach().contiguous().float()
+        dx = torch.empty_like(xs) if ld == S * K else torch.zeros_like(xs)
+        _n.call("spcl_group_l2norm_temp_backward", _n.ptr(xs), _n.ptr(dzs), rows, ld, S, K, normalize, c_float(T), _n.ptr(dx),
+                _n.stream())
+        return (dx.permute(0, 3, 1, 2) if dim == 4 else dx), None, None, None, None
+
+
+def group_l2norm_temp(logits, *, num_subheads, num_clusters, normalize, T=1.0):
+    """the cluster heads' ``Normalize() if normalize else Identical()`` then ``/ T`` on the logits of S subheads of K clusters:
+    [rows, >= S*K] rows or a logical [N, >= S*K, H, W] map.  No launch (the argument itself) when there is nothing to do."""
+    if not normalize and float(T) == 1.0:
+        return logits
+    return _GroupL2NormTempFn.apply(logits, int(num_subheads), int(num_clusters), bool(normalize), float(T))
 
 
 class _PixelCriterionFn(torch.autograd.Function):

@@ -24,7 +24,11 @@ pre-training as well.
 ``DiscreteMIConsistencyParams`` with ``PUILoss`` / ``PUISegLoss`` of contrastyou/losses/pica_loss.py as their criteria):
 ``feature_names``, ``pica_weights``, ``dense_paddings``, ``consistency_weight`` and ``lamda``.  The reference has the two
 criteria and pairs them with the cluster heads (``PICALossWrapper``, semi_seg/utils.py:242-263) but has no section for them;
-this one follows ``DiscreteMIConsistencyParams`` key for key.  Refused during pre-training like it."""
+this one follows ``DiscreteMIConsistencyParams`` key for key.  Refused during pre-training like it.
+``IICRegParameters`` builds the IIC-estimator baseline (``create_iic_estimator_hooks``: an ``IICEstimatorArray`` over the
+encoder and decoder features, one hook per estimator): the keys of config/specific/iic.yaml (``EncoderParams``,
+``DecoderParams``, ``LossParams``, ``weight``, ``enforce_matching``) plus ``feature_names`` and ``feature_importance``, which
+the reference's old-API ``IICTrainer`` (trainer.py:64-95) reads from ``FeatureExtractor``.  Refused during pre-training."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -41,6 +45,7 @@ _SEMI_SECTIONS = (
     ("MIDLPaperParameters", "create_midl_hook", False, False),
     ("MineParameters", "create_mine_hooks", True, False),
     ("PICAConsistencyParams", "create_pica_consistency_hook", True, False),
+    ("IICRegParameters", "create_iic_estimator_hooks", True, False),
 )
 
 

@@ -17,6 +17,7 @@ from ..arch.unet import sort_arch
 from .consistency import ConsistencyTrainerHook
 from .discretemi import DiscreteMITrainHook
 from .entmin import EntropyMinTrainerHook
+from .iic_estimator import IICEstimatorTrainHook
 from .infonce import INFONCEHook, SelfPacedINFONCEHook, decoder_names
 from .midl import MIDLPaperTrainerHook
 from .mine import MineTrainHook
@@ -179,4 +180,25 @@ def create_mine_hooks(*, model, feature_names: Union[str, List[str]], weights: U
     weights = ntuple(len(feature_names))(weights)
     hooks = [MineTrainHook(name=f"mine/{f.lower()}", model=model, feature_name=f, weight=w)
              for f, w in zip(feature_names, weights)]
+    return CombineTrainerHook(*hooks)
+
+
+def create_iic_estimator_hooks(*, model, feature_names: Union[str, List[str]], feature_importance=1.0, weight: float,
+                               EncoderParams: dict, DecoderParams: dict, LossParams: dict, enforce_matching: bool = False):
+    """``IICRegParameters`` (config/specific/iic.yaml, with the ``feature_names`` / ``feature_importance`` the old API read
+    from ``FeatureExtractor``): an ``IICEstimatorArray`` built as ``IICTrainer._init`` builds it (trainer.py:64-76) and one
+    hook ``iic/<feature>`` per estimator.  The reference multiplies the ``feature_importance``-weighted average of the
+    per-feature losses by ``weight`` (_mixins.py:93): hook weights ``weight * imp_i / sum(imp)`` are that sum.
+    ``LossParams.paddings`` lists one value per DECODER feature.  ``enforce_matching`` is read and, as in the reference, never
+    used."""
+    from ..mi_estimator.discrete_mi_estimator import IICEstimatorArray
+    feature_names = _listify(feature_names, 1)
+    importance = [float(v) for v in ntuple(len(feature_names))(feature_importance)]
+    array = IICEstimatorArray()
+    array.add_encoder_interface(feature_names=feature_names, model=model, **EncoderParams)
+    array.add_decoder_interface(feature_names=feature_names, model=model, **DecoderParams, **LossParams)
+    total = sum(importance)
+    hooks = [IICEstimatorTrainHook(name=f"iic/{f.lower()}", model=model, feature_name=f, estimator=array[f],
+                                   weight=float(weight) * imp / total)
+             for f, imp in zip(feature_names, importance)]
     return CombineTrainerHook(*hooks)
