@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 26
+#define SPCL_ABI_VERSION 27
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -707,6 +707,28 @@ size_t spcl_surface_3d_workspace_bytes(int V, int D, int H, int W, int n_report)
 int spcl_surface_distances_3d(const int64_t* pred, const int64_t* target, int V, int D, int H, int W, int C, const int* report,
                               int n_report, double sz, double sy, double sx, double percentile, double* hd, double* mhd,
                               double* asd, uint8_t* empty, void* ws, size_t ws_bytes, void* stream);
+
+/* Largest connected component per foreground class and volume (csrc/components.hip): the post-processing step segmentation
+ * results are usually reported after.  NOT in the reference; inference opts into it (InferenceEpocher(postprocess=...)).
+ *   labels  [V][D][H][W] int64 class-coded maps, read only;  out  the same shape, may NOT alias labels (SPCL_EINVAL)
+ *   classes n_classes (1 .. 15) HOST ints, distinct, each in [1, C): the classes to process; 0 is the fill value.  C >= 2.
+ *   A component is a maximal set of voxels of ONE label value joined through 6-neighbour steps (+-z, +-y, +-x) inside its
+ *   volume -- the neighbourhood of spcl_surface_distances_3d's borders; D = 1: 4-neighbour components per slice ([B][H][W]
+ *   slice-wise is V = B, D = 1).  Diagonal contact does not connect.
+ *   For every listed class the largest component by voxel count keeps its label in `out`, every other voxel of the class
+ *   becomes 0.  Equal sizes: the component whose smallest linear index (z*H + y)*W + x is smallest wins -- what
+ *   numpy.argmax(numpy.bincount(...)) picks on scipy.ndimage.label output (components numbered in raster order of their first
+ *   voxel, first maximum).  Voxels whose label is not listed (background, unlisted classes, values outside [0, C)) are copied
+ *   unchanged, form no components and join nothing.
+ *   kept_size    [V][n_classes] int64  voxel count of the kept component of classes[i] (0: the class is absent)
+ *   n_components [V][n_classes] int32  number of components the class had
+ * D H W < 2^31.  ws: spcl_largest_component_workspace_bytes(V, D, H, W, n_classes) bytes (0 = unsupported shape), 16-byte
+ * aligned: three uint32 words per voxel (union-find parents, flat roots, sizes) and one 64-bit word per (volume, class).
+ * Five launches on `stream`, integer atomics only (the same input gives the same bits), nothing is read back or allocated:
+ * the call can be captured.  Every argument is checked before the first launch. */
+size_t spcl_largest_component_workspace_bytes(int V, int D, int H, int W, int n_classes);
+int spcl_largest_component(const int64_t* labels, int V, int D, int H, int W, int C, const int* classes, int n_classes,
+                           int64_t* out, int64_t* kept_size, int32_t* n_components, void* ws, size_t ws_bytes, void* stream);
 
 /* Decoder data movement (NHWC, CS a multiple of 16): nn.Upsample(scale_factor=2) of `_UpConv` (unet.py:89) and its
  * backward (H, W = the low-resolution size in both calls), torch.cat((skip, up), dim=1) (unet.py:194-224) and its

@@ -2797,6 +2797,52 @@ def surface_distances_3d(pred: torch.Tensor, target: torch.Tensor, C: int, repor
     return vals[0], vals[1], vals[2], empty
 
 
+_LCC_WS = {}  # (device, V, D, H, W, n_classes) -> workspace, reused as _SURFACE_WS is
+
+
+def largest_components(labels: torch.Tensor, num_classes: int, classes=None, volumetric: bool = True, out=None):
+    """Keep the largest connected component of every listed foreground class (``spcl_largest_component``): ``labels`` is a
+    class-coded integer ``[D,H,W]`` or ``[V,D,H,W]`` map; with ``volumetric=False`` a ``[B,H,W]`` map is ``B`` independent
+    slices (4-neighbour components; a 4-D map is refused there), with ``volumetric=True`` it is ONE volume (6-neighbour), as
+    ``surface_distances_3d`` reads it.  -> the processed int64 map in the shape of ``labels``: every voxel of a listed class outside that class's
+    largest component becomes 0 (equal sizes: the component that starts first in raster order, as ``scipy.ndimage.label`` +
+    ``argmax(bincount)`` decide), everything else is copied.  ``classes``: None = ``range(1, num_classes)``, else distinct
+    classes in ``[1, num_classes)``, at most 15.  A list passed as ``out`` receives ``(kept_size, n_components)``: int64 / int32
+    ``[V, n_classes]`` device tensors (as ``ucmt_softmax_mse(out=)`` hands over its extras).  Everything stays on the device."""
+    if labels.dim() not in (3, 4) or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise TypeError("largest_components takes class-coded integer [D,H,W] or [V,D,H,W] maps, given "
+                        f"{tuple(labels.shape)} {labels.dtype}")
+    _n.require_gpu(labels)
+    C = int(num_classes)
+    cls = list(range(1, C)) if classes is None else [int(c) for c in classes]
+    if C < 2 or not 1 <= len(cls) <= 15 or any(not 1 <= c < C for c in cls) or len(set(cls)) != len(cls):
+        raise ValueError(f"largest_components: `classes` must be 1 to 15 distinct classes in [1, {C}) (0 is the fill value), "
+                         f"given {cls}")
+    lab = labels.detach().long().contiguous()
+    shape = lab.shape
+    if lab.dim() == 3:
+        lab = lab.unsqueeze(0) if volumetric else lab.unsqueeze(1)
+    elif not volumetric:
+        raise ValueError("largest_components(volumetric=False) takes [B,H,W] slices")
+    V, D, H, W = lab.shape
+    R, dev = len(cls), lab.device
+    key = (dev, V, D, H, W, R)
+    ws = _LCC_WS.get(key)
+    if ws is None:
+        nbytes = _n.call("spcl_largest_component_workspace_bytes", V, D, H, W, R)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None  # (0: the call below says why)
+        if ws is not None:
+            _LCC_WS[key] = ws
+    processed = torch.empty_like(lab)
+    kept = torch.empty((V, R), dtype=torch.int64, device=dev)
+    ncomp = torch.empty((V, R), dtype=torch.int32, device=dev)
+    _n.call("spcl_largest_component", _n.ptr(lab), V, D, H, W, C, (c_int * R)(*cls), R, _n.ptr(processed), _n.ptr(kept),
+            _n.ptr(ncomp), _n.ptr(ws), ws.numel() if ws is not None else 0, _n.stream())
+    if out is not None:
+        out.extend((kept, ncomp))
+    return processed.view(shape)
+
+
 class _Upsample2xFn(torch.autograd.Function):
     """nn.Upsample(scale_factor=2) (nearest) of ``_UpConv`` on NHWC storage; backward = 2x2 sum."""
 

@@ -209,11 +209,22 @@ class InferenceEpocher(EvalEpocher):
     ``functional.surface_distances_3d`` call per batch with ``voxelspacing`` (None, one float or ``(sz, sy, sx)``).  Each
     batch is taken as one volume, its slices in batch order along z: the validation loaders hand over one scan per batch
     (``ScanBatchSampler``) and the stores list a scan's slices in file-name order, which is z order for the reference's
-    zero-padded slice names.  A batch that mixes scan names is not a volume and raises ``ValueError``."""
+    zero-padded slice names.  A batch that mixes scan names is not a volume and raises ``ValueError``.
+
+    ``postprocess="largest_component"`` (None by default: meters, keys, values and PNGs are then unchanged; the step is not in
+    the reference) additionally sends every batch's arg-max map through ``functional.largest_components`` -- per scan under
+    ``volumetric=True``, per slice otherwise -- and feeds the result to meters registered BESIDE the others: ``dice_lcc``,
+    ``hd_lcc``, with ``volumetric=True`` ``hd3d_lcc`` / ``mhd3d_lcc`` / ``asd3d_lcc``, and ``lcc_removed``, the mean fraction of
+    a batch's foreground voxels the step removed.  The processed maps go to ``save_dir/pred_lcc``.  ``get_score()`` stays the
+    unprocessed ``DSC_mean``."""
     VOLUME_METERS = (("hd3d", "hausdorff"), ("mhd3d", "mod_hausdorff"), ("asd3d", "average_surface"))
+    POSTPROCESS = (None, "largest_component")
 
     def __init__(self, *, model: nn.Module, loader: Iterable, sup_criterion, cur_epoch=0, device="cuda",
-                 graph: Optional[bool] = None, volumetric: bool = False, voxelspacing=None):
+                 graph: Optional[bool] = None, volumetric: bool = False, voxelspacing=None, postprocess=None):
+        if postprocess not in self.POSTPROCESS:
+            raise ValueError(f"InferenceEpocher: postprocess must be one of {self.POSTPROCESS}, given {postprocess!r}")
+        self._postprocess = postprocess
         self._volumetric, self._voxelspacing = bool(volumetric), voxelspacing  # (configure_meters runs inside __init__)
         super().__init__(model=model, loader=loader, sup_criterion=sup_criterion, cur_epoch=cur_epoch, device=device,
                          graph=graph)
@@ -228,7 +239,35 @@ class InferenceEpocher(EvalEpocher):
         if self._volumetric:
             for name, metername in self.VOLUME_METERS:
                 meters.register_meter(name, VolumeSurfaceMeter(C=C, report_axises=list(range(1, C)), metername=metername))
+        if self._postprocess is not None:
+            meters.register_meter("dice_lcc", UniversalDice(C, report_axises=list(range(1, C))))
+            meters.register_meter("hd_lcc", SurfaceMeter(C=C, report_axises=list(range(1, C)), metername="hausdorff"))
+            if self._volumetric:
+                for name, metername in self.VOLUME_METERS:
+                    meters.register_meter(name + "_lcc",
+                                          VolumeSurfaceMeter(C=C, report_axises=list(range(1, C)), metername=metername))
+            meters.register_meter("lcc_removed", AverageValueMeter())
         return meters
+
+    def _postprocessed(self, prediction, eval_target, file_path, group):
+        """the ``postprocess="largest_component"`` side of one batch: processed map -> its meters and ``pred_lcc/`` PNGs"""
+        from .helper import write_predict
+        target = eval_target.squeeze(1)
+        processed = F_hip.largest_components(prediction, self.num_classes, volumetric=self._volumetric)
+        write_predict(processed, self._save_dir, file_path, folder="pred_lcc")
+        dice = self.meters["dice_lcc"]
+        inter, union = F_hip.dice_counts(processed, target, self.num_classes)
+        dice.add_counts(inter, union, dice.group_names_for(inter.shape[0], list(group)))
+        self.meters["hd_lcc"].add(processed, target)
+        if self._volumetric:
+            distances = F_hip.surface_distances_3d(processed, target, self.num_classes, list(range(1, self.num_classes)),
+                                                   self._voxelspacing, 95.0)
+            for name, _ in self.VOLUME_METERS:
+                self.meters[name + "_lcc"].add_distances(*distances)
+        # removed fraction of the batch's foreground voxels, as a device scalar (0 where the prediction holds no foreground);
+        # the step only ever turns foreground into 0, so the processed foreground is a subset
+        before, after = (prediction != 0).sum(), (processed != 0).sum()
+        self.meters["lcc_removed"].add(((before - after).double() / before.clamp(min=1).double()).float())
 
     @torch.no_grad()
     def _run_eval(self):
@@ -252,6 +291,8 @@ class InferenceEpocher(EvalEpocher):
                                                        list(range(1, self.num_classes)), self._voxelspacing, 95.0)
                 for name, _ in self.VOLUME_METERS:
                     self.meters[name].add_distances(*distances)
+            if self._postprocess is not None:
+                self._postprocessed(prediction, eval_target, file_path, group)
 
 
 class FineTuneEpocher(_EpocherBase):

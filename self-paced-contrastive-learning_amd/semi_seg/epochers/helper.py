@@ -175,9 +175,10 @@ def _write_pngs(maps: torch.Tensor, folder: str, filenames):
         Image.fromarray(a, mode="L").save(path)
 
 
-def write_predict(predict_logit: torch.Tensor, save_dir: str, filenames):
+def write_predict(predict_logit: torch.Tensor, save_dir: str, filenames, folder: str = "pred"):
     """``write_predict`` (semi_seg/epochers/helper.py:78-85): the arg-max map of every sample to ``save_dir/pred``.  A
-    [B,K,H,W] class map is reduced with the HIP arg-max; a [B,H,W] integer map is taken as the arg-max already formed."""
+    [B,K,H,W] class map is reduced with the HIP arg-max; a [B,H,W] integer map is taken as the arg-max already formed.
+    ``folder`` names another sub-folder of ``save_dir`` (the post-processed maps go to ``pred_lcc``)."""
     import os
     if isinstance(filenames, str):
         filenames = [filenames]
@@ -185,7 +186,7 @@ def write_predict(predict_logit: torch.Tensor, save_dir: str, filenames):
         from ... import functional as F_hip
         predict_logit = F_hip.argmax_classes(predict_logit)
     assert predict_logit.dim() == 3 and not predict_logit.is_floating_point(), predict_logit.shape
-    _write_pngs(predict_logit, os.path.join(save_dir, "pred"), list(filenames))
+    _write_pngs(predict_logit, os.path.join(save_dir, folder), list(filenames))
 
 
 def write_img_target(image: torch.Tensor, target: torch.Tensor, save_dir: str, filenames):

@@ -117,13 +117,16 @@ class FineTuneTrainer:
             _sg.gc_release()  # (the epochers' captures keep the collector's heap frozen from one epoch to the next)
         return self.history
 
-    def inference(self, checkpoint=None, *, volumetric=False, voxelspacing=None):
+    def inference(self, checkpoint=None, *, volumetric=False, voxelspacing=None, postprocess=None):
         """``Trainer.inference`` (semi_seg/trainers/base.py:127-148): load the model of a checkpoint -- ``None``: this
         trainer's ``save_dir/best.pth``; a ``.pth`` file; or a directory holding a ``best.pth`` --, run ``InferenceEpocher``
         over the test loader (loss, Dice, Hausdorff distance; PNGs of image, label and prediction under ``save_dir``) and
         return ``(statistics, DSC_mean)``.  ``volumetric=True`` adds the per-scan 3-D surface distances ``hd3d`` / ``mhd3d`` /
         ``asd3d`` under ``voxelspacing`` = ``(sz, sy, sx)``: every test batch must then be one scan, slices in z order (the
-        stores list a scan's slices in file-name order, which is z order for the reference's zero-padded names)."""
+        stores list a scan's slices in file-name order, which is z order for the reference's zero-padded names).
+        ``postprocess="largest_component"`` adds the ``*_lcc`` meters, ``lcc_removed`` and the ``pred_lcc`` PNGs of the
+        prediction reduced to the largest connected component of every foreground class (``InferenceEpocher``); the returned
+        score stays the unprocessed ``DSC_mean``."""
         if checkpoint is None:
             if not self._save_dir:
                 raise FileNotFoundError("inference(): no checkpoint given and the trainer has no save_dir")
@@ -146,7 +149,7 @@ class FineTuneTrainer:
         self._model.load_state_dict(torch.load(path, map_location="cpu")["_model"])
         evaler = InferenceEpocher(model=self._model, loader=self._test_loader, sup_criterion=self._criterion,
                                   cur_epoch=self._cur_epoch, device=self._device, volumetric=volumetric,
-                                  voxelspacing=voxelspacing)
+                                  voxelspacing=voxelspacing, postprocess=postprocess)
         evaler.init(save_dir=self._save_dir)
         result = evaler.run()
         return result, evaler.get_score()
