@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 27
+#define SPCL_ABI_VERSION 28
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -729,6 +729,28 @@ int spcl_surface_distances_3d(const int64_t* pred, const int64_t* target, int V,
 size_t spcl_largest_component_workspace_bytes(int V, int D, int H, int W, int n_classes);
 int spcl_largest_component(const int64_t* labels, int V, int D, int H, int W, int C, const int* classes, int n_classes,
                            int64_t* out, int64_t* kept_size, int32_t* n_components, void* ws, size_t ws_bytes, void* stream);
+
+/* Test-time augmentation: the merge of V views' class maps (csrc/tta.hip).  NOT in the reference; inference opts into it
+ * (InferenceEpocher(tta=...)).  The entropy is the normalised one the uncertainty-aware mean teacher thresholds
+ * (semi_seg/epochers/comparable.py:94-98: Entropy(softmax(.)) / log(C), eps 1e-16), here of the averaged prediction.
+ *   views  a HOST array of V (1, 2, 4 or 8) device pointers to f32 class logits [N][H][W][C], 2 <= C <= 16, handed to the
+ *          kernel by value -- nothing is uploaded;  ops  V HOST bytes, each < 8: bit 0 the view's input was flipped along H,
+ *          bit 1 along W, bit 2 its H and W axes were swapped AFTER the flips (needs H == W, else SPCL_EINVAL).
+ *   Per output pixel (n, u, v), u' = bit 0 ? H-1-u : u, v' = bit 1 ? W-1-v : v: view j is read at (n, u', v'), with bit 2 at
+ *   row v', column u'; no un-flipped or transposed copy is written.  q_j = softmax of that row (exp(x - max), a true division
+ *   by the sum); the V rows are added pairwise in a fixed balanced tree over the view index ((0+1), (2+3), ..., then those
+ *   sums) and multiplied by the exact 1 / V: V equal rows give back their common value bit for bit.
+ *   prob          [N][H][W][C] f32  the mean probability p; may not overlap a view
+ *   pred          [N][H][W] int64   the first maximal class of p (the tie rule of spcl_argmax_classes)
+ *   entropy       [N][H][W] f32, may be NULL   -sum_c p_c log(p_c + eps) / log(C)
+ *   mean_entropy  f32 scalar        the mean of that entropy over the N H W pixels: per-workgroup double partials added in
+ *                                   index order by the last workgroup (bitwise reproducible, no second launch)
+ * N H W < 2^31.  ws: spcl_tta_merge_workspace_bytes(N, H, W) bytes, 8-byte aligned.  One launch and the ticket's memset on
+ * `stream`, one thread per pixel, 16-byte accesses where C == 4 and every pointer is 16-byte aligned; nothing is read back or
+ * allocated: the call can be captured.  Every argument is checked before the memset. */
+size_t spcl_tta_merge_workspace_bytes(int N, int H, int W);
+int spcl_tta_merge(const float* const* views, const uint8_t* ops, int V, int N, int C, int H, int W, float eps, float* prob,
+                   int64_t* pred, float* entropy, float* mean_entropy, void* ws, size_t ws_bytes, void* stream);
 
 /* Decoder data movement (NHWC, CS a multiple of 16): nn.Upsample(scale_factor=2) of `_UpConv` (unet.py:89) and its
  * backward (H, W = the low-resolution size in both calls), torch.cat((skip, up), dim=1) (unet.py:194-224) and its

@@ -2843,6 +2843,84 @@ def largest_components(labels: torch.Tensor, num_classes: int, classes=None, vol
     return processed.view(shape)
 
 
+# ------------------------------------------------------------------------------- test-time augmentation (csrc/tta.hip)
+# The op byte of a view: bit 0 its input was flipped along H, bit 1 along W, bit 2 its H and W axes were swapped AFTER the
+# flips.  "flips" is the group of the two mirrors, "dihedral" the eight symmetries of the square.
+TTA_MODES = {"flips": (0, 1, 2, 3), "dihedral": (0, 1, 2, 3, 4, 5, 6, 7)}
+TTA_VIEW_COUNTS = (1, 2, 4, 8)  # the merge's pairwise tree is balanced
+_TTA_WS = {}  # (device, N, H, W) -> workspace, reused as _SURFACE_WS is
+_TTA_FLAGS = {}  # (device, N, flip bits) -> uint8 [N] flags of ``flip_batch``, every sample the same
+
+
+def _tta_ops(mode, H, W):
+    """the op bytes of ``mode`` for an H x W image; host only.  An unknown mode and "dihedral" on a non-square image raise
+    ``ValueError``."""
+    if mode not in TTA_MODES:
+        raise ValueError(f"tta mode must be one of {tuple(TTA_MODES)}, given {mode!r}")
+    ops = TTA_MODES[mode]
+    if any(op & 4 for op in ops) and H != W:
+        raise ValueError(f"tta mode {mode!r} swaps the image axes and needs a square image, given {H} x {W}")
+    return ops
+
+
+def _tta_view(image, op):
+    """view ``op`` of an [N, 1, H, W] batch: flipped along H (bit 0) and W (bit 1) by ``flip_batch``, then its axes swapped
+    (bit 2).  Op 0 is ``image`` itself, not a copy."""
+    view = image
+    if op & 3:
+        _n.require_gpu(image)
+        key = (image.device, image.shape[0], op & 3)
+        flags = _TTA_FLAGS.get(key)
+        if flags is None:
+            flags = _TTA_FLAGS[key] = torch.full((image.shape[0],), op & 3, dtype=torch.uint8, device=image.device)
+        view = flip_batch(view, flags)
+    if op & 4:
+        view = view.transpose(-1, -2).contiguous()
+    return view
+
+
+def tta_views(image, mode):
+    """``[(view_image, op), ...]`` of an [N, 1, H, W] batch for ``mode`` = "flips" (ops 0 - 3) or "dihedral" (ops 0 - 7, square
+    images only: ``ValueError`` on the host before any device work).  View 0 is ``image`` itself."""
+    if image.dim() != 4:
+        raise ValueError(f"tta_views takes an [N, C, H, W] batch, given {tuple(image.shape)}")
+    return [(_tta_view(image, op), op) for op in _tta_ops(mode, image.shape[-2], image.shape[-1])]
+
+
+def tta_merge(view_logits, ops, eps=1e-16, want_entropy=True):
+    """Merge the class logits of V views (``spcl_tta_merge``, one launch): ``view_logits[j]`` is the logical [N, C, H, W] map
+    the network returned for the view with op byte ``ops[j]``, in THAT view's frame.  -> ``(prob, pred, entropy,
+    mean_entropy)`` in the original frame: the mean over the views of their softmax (a logical [N, C, H, W] view of
+    channels-last storage; the V rows are added in a balanced pairwise tree, so V exact copies merge to the bits of one),
+    its first maximal class (int64 [N, H, W]), its normalised entropy ``-sum p log(p + eps) / log(C)`` (f32 [N, H, W]; None
+    without ``want_entropy``) and the mean of that entropy (an f32 device scalar).  Everything stays on the device."""
+    maps, ops = list(view_logits), [int(op) for op in ops]
+    if len(maps) not in TTA_VIEW_COUNTS:
+        raise ValueError(f"tta_merge: {len(maps)} views (1, 2, 4 or 8)")
+    if len(ops) != len(maps):
+        raise ValueError(f"tta_merge: {len(maps)} views and {len(ops)} ops")
+    if any(not 0 <= op < 8 for op in ops):
+        raise ValueError(f"tta_merge: every op must be in [0, 8), given {ops}")
+    if any(t.dim() != 4 or tuple(t.shape) != tuple(maps[0].shape) or t.device != maps[0].device for t in maps):
+        raise ValueError(f"tta_merge: the views' maps differ: {[tuple(t.shape) for t in maps]}")
+    _n.require_gpu(*maps)
+    stores = [_class_map_storage(t.detach()) for t in maps]
+    N, H, W, C = stores[0].shape
+    dev = stores[0].device
+    key = (dev, N, H, W)
+    ws = _TTA_WS.get(key)
+    if ws is None:
+        ws = _TTA_WS[key] = torch.empty(_n.call("spcl_tta_merge_workspace_bytes", N, H, W), dtype=torch.uint8, device=dev)
+    prob = torch.empty((N, H, W, C), dtype=torch.float32, device=dev)
+    pred = torch.empty((N, H, W), dtype=torch.int64, device=dev)
+    entropy = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_entropy else None
+    mean_entropy = torch.empty((), dtype=torch.float32, device=dev)
+    _n.call("spcl_tta_merge", _n.ptr_array(stores), (ctypes.c_uint8 * len(ops))(*ops), len(ops), N, C, H, W,
+            c_float(float(eps)), _n.ptr(prob), _n.ptr(pred), _n.ptr(entropy), _n.ptr(mean_entropy), _n.ptr(ws), ws.numel(),
+            _n.stream())
+    return prob.permute(0, 3, 1, 2), pred, entropy, mean_entropy
+
+
 class _Upsample2xFn(torch.autograd.Function):
     """nn.Upsample(scale_factor=2) (nearest) of ``_UpConv`` on NHWC storage; backward = 2x2 sum."""
 

@@ -134,12 +134,16 @@ class EvalEpocher(_EpocherBase):
 
     def _batch_with_prediction(self, eval_img, eval_target):
         """``_batch`` and the arg-max map its Dice counts were taken from -> (loss, intersections, unions, prediction)"""
+        return self._batch_with_logits(eval_img, eval_target)[:4]
+
+    def _batch_with_logits(self, eval_img, eval_target):
+        """``_batch_with_prediction`` and the logits behind it -> (loss, intersections, unions, prediction, logits)"""
         eval_logits = self._model(eval_img)
         onehot_target = class2one_hot(eval_target.squeeze(1), self.num_classes)
         eval_loss = self._sup_criterion(F_hip.softmax_classes(eval_logits), onehot_target, disable_assert=True)
         prediction = F_hip.argmax_classes(eval_logits)
         inter, union = F_hip.dice_counts(prediction, eval_target.squeeze(1), self.num_classes)
-        return eval_loss, inter, union, prediction
+        return eval_loss, inter, union, prediction, eval_logits
 
     def _batch_replayed(self, graphs, eval_img, eval_target):
         """``_batch`` from a hipGraph of this shape: first sight eager (lazily created workspaces are then outside any
@@ -216,15 +220,29 @@ class InferenceEpocher(EvalEpocher):
     ``volumetric=True``, per slice otherwise -- and feeds the result to meters registered BESIDE the others: ``dice_lcc``,
     ``hd_lcc``, with ``volumetric=True`` ``hd3d_lcc`` / ``mhd3d_lcc`` / ``asd3d_lcc``, and ``lcc_removed``, the mean fraction of
     a batch's foreground voxels the step removed.  The processed maps go to ``save_dir/pred_lcc``.  ``get_score()`` stays the
-    unprocessed ``DSC_mean``."""
+    unprocessed ``DSC_mean``.
+
+    ``tta="flips"`` / ``"dihedral"`` (None by default: meters, keys, values, PNGs and launches are then unchanged; the step is
+    not in the reference) adds test-time augmentation BESIDE the plain pass: the plain logits are view 0, every other view of
+    ``functional.tta_views`` (the two mirrors; with "dihedral", square images only, also the axis swap) is one more forward of
+    the batch's own size, and ``functional.tta_merge`` averages the views' probabilities in the plain frame in one launch.
+    The merged map feeds ``loss_tta`` (the supervised criterion on the mean probability), ``dice_tta``, ``hd_tta``, with
+    ``volumetric=True`` ``hd3d_tta`` / ``mhd3d_tta`` / ``asd3d_tta``, with ``postprocess`` the same step into ``dice_tta_lcc``,
+    ``hd_tta_lcc``, the volumetric ``*_tta_lcc`` and ``lcc_removed_tta``; ``tta_entropy`` is the mean normalised entropy of the
+    merged probability and ``tta_changed`` the fraction of a batch's pixels whose merged class differs from the plain one
+    (both added as device scalars).  PNGs: ``pred_tta/``, with ``postprocess`` ``pred_tta_lcc/``, and ``uncertainty_tta/``
+    (``round(255 * entropy)``).  ``get_score()`` stays the plain ``DSC_mean``."""
     VOLUME_METERS = (("hd3d", "hausdorff"), ("mhd3d", "mod_hausdorff"), ("asd3d", "average_surface"))
     POSTPROCESS = (None, "largest_component")
+    TTA = (None,) + tuple(F_hip.TTA_MODES)
 
     def __init__(self, *, model: nn.Module, loader: Iterable, sup_criterion, cur_epoch=0, device="cuda",
-                 graph: Optional[bool] = None, volumetric: bool = False, voxelspacing=None, postprocess=None):
+                 graph: Optional[bool] = None, volumetric: bool = False, voxelspacing=None, postprocess=None, tta=None):
         if postprocess not in self.POSTPROCESS:
             raise ValueError(f"InferenceEpocher: postprocess must be one of {self.POSTPROCESS}, given {postprocess!r}")
-        self._postprocess = postprocess
+        if tta not in self.TTA:
+            raise ValueError(f"InferenceEpocher: tta must be one of {self.TTA}, given {tta!r}")
+        self._postprocess, self._tta = postprocess, tta
         self._volumetric, self._voxelspacing = bool(volumetric), voxelspacing  # (configure_meters runs inside __init__)
         super().__init__(model=model, loader=loader, sup_criterion=sup_criterion, cur_epoch=cur_epoch, device=device,
                          graph=graph)
@@ -239,35 +257,74 @@ class InferenceEpocher(EvalEpocher):
         if self._volumetric:
             for name, metername in self.VOLUME_METERS:
                 meters.register_meter(name, VolumeSurfaceMeter(C=C, report_axises=list(range(1, C)), metername=metername))
-        if self._postprocess is not None:
-            meters.register_meter("dice_lcc", UniversalDice(C, report_axises=list(range(1, C))))
-            meters.register_meter("hd_lcc", SurfaceMeter(C=C, report_axises=list(range(1, C)), metername="hausdorff"))
-            if self._volumetric:
-                for name, metername in self.VOLUME_METERS:
-                    meters.register_meter(name + "_lcc",
-                                          VolumeSurfaceMeter(C=C, report_axises=list(range(1, C)), metername=metername))
-            meters.register_meter("lcc_removed", AverageValueMeter())
+        for tag in ("",) if self._tta is None else ("", "_tta"):  # (the plain pass's meters first, in the order they had)
+            if tag:
+                meters.register_meter("loss_tta", AverageValueMeter())
+                meters.register_meter("dice_tta", UniversalDice(C, report_axises=list(range(1, C))))
+                meters.register_meter("hd_tta", SurfaceMeter(C=C, report_axises=list(range(1, C)), metername="hausdorff"))
+                if self._volumetric:
+                    for name, metername in self.VOLUME_METERS:
+                        meters.register_meter(name + tag,
+                                              VolumeSurfaceMeter(C=C, report_axises=list(range(1, C)), metername=metername))
+            if self._postprocess is not None:
+                meters.register_meter(f"dice{tag}_lcc", UniversalDice(C, report_axises=list(range(1, C))))
+                meters.register_meter(f"hd{tag}_lcc", SurfaceMeter(C=C, report_axises=list(range(1, C)), metername="hausdorff"))
+                if self._volumetric:
+                    for name, metername in self.VOLUME_METERS:
+                        meters.register_meter(name + tag + "_lcc",
+                                              VolumeSurfaceMeter(C=C, report_axises=list(range(1, C)), metername=metername))
+                meters.register_meter("lcc_removed" + tag, AverageValueMeter())
+        if self._tta is not None:
+            meters.register_meter("tta_entropy", AverageValueMeter())
+            meters.register_meter("tta_changed", AverageValueMeter())
         return meters
 
-    def _postprocessed(self, prediction, eval_target, file_path, group):
-        """the ``postprocess="largest_component"`` side of one batch: processed map -> its meters and ``pred_lcc/`` PNGs"""
+    def _postprocessed(self, prediction, eval_target, file_path, group, tag=""):
+        """the ``postprocess="largest_component"`` side of one batch: processed map -> its meters and ``pred_lcc/`` PNGs
+        (``tag="_tta"``: of the merged prediction, into ``*_tta_lcc``, ``lcc_removed_tta`` and ``pred_tta_lcc/``)"""
         from .helper import write_predict
         target = eval_target.squeeze(1)
         processed = F_hip.largest_components(prediction, self.num_classes, volumetric=self._volumetric)
-        write_predict(processed, self._save_dir, file_path, folder="pred_lcc")
-        dice = self.meters["dice_lcc"]
+        write_predict(processed, self._save_dir, file_path, folder=f"pred{tag}_lcc")
+        dice = self.meters[f"dice{tag}_lcc"]
         inter, union = F_hip.dice_counts(processed, target, self.num_classes)
         dice.add_counts(inter, union, dice.group_names_for(inter.shape[0], list(group)))
-        self.meters["hd_lcc"].add(processed, target)
+        self.meters[f"hd{tag}_lcc"].add(processed, target)
         if self._volumetric:
             distances = F_hip.surface_distances_3d(processed, target, self.num_classes, list(range(1, self.num_classes)),
                                                    self._voxelspacing, 95.0)
             for name, _ in self.VOLUME_METERS:
-                self.meters[name + "_lcc"].add_distances(*distances)
+                self.meters[name + tag + "_lcc"].add_distances(*distances)
         # removed fraction of the batch's foreground voxels, as a device scalar (0 where the prediction holds no foreground);
         # the step only ever turns foreground into 0, so the processed foreground is a subset
         before, after = (prediction != 0).sum(), (processed != 0).sum()
-        self.meters["lcc_removed"].add(((before - after).double() / before.clamp(min=1).double()).float())
+        self.meters["lcc_removed" + tag].add(((before - after).double() / before.clamp(min=1).double()).float())
+
+    def _augmented(self, eval_img, eval_logits, prediction, eval_target, file_path, group):
+        """the ``tta`` side of one batch: the plain logits are view 0, one more forward per further view, one merge launch;
+        the merged map -> its meters and the ``pred_tta/``, ``uncertainty_tta/`` (and ``pred_tta_lcc/``) PNGs"""
+        from .helper import write_predict, write_uncertainty
+        views = F_hip.tta_views(eval_img, self._tta)
+        view_logits = [eval_logits] + [self._model(view) for view, _ in views[1:]]
+        prob, merged, entropy, mean_entropy = F_hip.tta_merge(view_logits, [op for _, op in views])
+        target = eval_target.squeeze(1)
+        write_predict(merged, self._save_dir, file_path, folder="pred_tta")
+        write_uncertainty(entropy, self._save_dir, file_path, folder="uncertainty_tta")
+        onehot_target = class2one_hot(target, self.num_classes)
+        self.meters["loss_tta"].add(self._sup_criterion(prob, onehot_target, disable_assert=True))
+        dice = self.meters["dice_tta"]
+        inter, union = F_hip.dice_counts(merged, target, self.num_classes)
+        dice.add_counts(inter, union, dice.group_names_for(inter.shape[0], list(group)))
+        self.meters["hd_tta"].add(merged, target)
+        if self._volumetric:
+            distances = F_hip.surface_distances_3d(merged, target, self.num_classes, list(range(1, self.num_classes)),
+                                                   self._voxelspacing, 95.0)
+            for name, _ in self.VOLUME_METERS:
+                self.meters[name + "_tta"].add_distances(*distances)
+        if self._postprocess is not None:
+            self._postprocessed(merged, eval_target, file_path, group, tag="_tta")
+        self.meters["tta_entropy"].add(mean_entropy)
+        self.meters["tta_changed"].add((merged != prediction).float().mean())
 
     @torch.no_grad()
     def _run_eval(self):
@@ -279,7 +336,7 @@ class InferenceEpocher(EvalEpocher):
             eval_img, eval_target, file_path, _, group = unzip_single_transformed(eval_data, self._device)
             if self._volumetric and len(set(group)) != 1:
                 raise ValueError(f"InferenceEpocher(volumetric=True): a batch is one scan, this one mixes {sorted(set(group))}")
-            eval_loss, inter, union, prediction = self._batch_with_prediction(eval_img, eval_target)
+            eval_loss, inter, union, prediction, eval_logits = self._batch_with_logits(eval_img, eval_target)
             write_img_target(eval_img, eval_target, self._save_dir, file_path)
             write_predict(prediction, self._save_dir, file_path)
             self.meters["loss"].add(eval_loss)
@@ -293,6 +350,8 @@ class InferenceEpocher(EvalEpocher):
                     self.meters[name].add_distances(*distances)
             if self._postprocess is not None:
                 self._postprocessed(prediction, eval_target, file_path, group)
+            if self._tta is not None:
+                self._augmented(eval_img, eval_logits, prediction, eval_target, file_path, group)
 
 
 class FineTuneEpocher(_EpocherBase):

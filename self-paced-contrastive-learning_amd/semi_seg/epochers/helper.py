@@ -189,6 +189,16 @@ def write_predict(predict_logit: torch.Tensor, save_dir: str, filenames, folder:
     _write_pngs(predict_logit, os.path.join(save_dir, folder), list(filenames))
 
 
+def write_uncertainty(entropy: torch.Tensor, save_dir: str, filenames, folder: str = "uncertainty_tta"):
+    """a [B,H,W] map of normalised entropies in [0, 1] to ``save_dir/folder`` as ``round(255 * entropy)``, one 8-bit PNG per
+    sample (not in the reference: the uncertainty map of the test-time-augmented prediction)"""
+    import os
+    if isinstance(filenames, str):
+        filenames = [filenames]
+    assert entropy.dim() == 3 and entropy.is_floating_point(), (tuple(entropy.shape), entropy.dtype)
+    _write_pngs((entropy * 255).round().clamp(0, 255), os.path.join(save_dir, folder), list(filenames))
+
+
 def write_img_target(image: torch.Tensor, target: torch.Tensor, save_dir: str, filenames):
     """``write_img_target`` (semi_seg/epochers/helper.py:88-97): ``image * 255`` to ``save_dir/img`` and the label map to
     ``save_dir/gt``, one PNG per sample ([B,1,H,W] or [B,H,W] tensors)"""

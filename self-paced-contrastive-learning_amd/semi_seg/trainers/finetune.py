@@ -117,7 +117,7 @@ class FineTuneTrainer:
             _sg.gc_release()  # (the epochers' captures keep the collector's heap frozen from one epoch to the next)
         return self.history
 
-    def inference(self, checkpoint=None, *, volumetric=False, voxelspacing=None, postprocess=None):
+    def inference(self, checkpoint=None, *, volumetric=False, voxelspacing=None, postprocess=None, tta=None):
         """``Trainer.inference`` (semi_seg/trainers/base.py:127-148): load the model of a checkpoint -- ``None``: this
         trainer's ``save_dir/best.pth``; a ``.pth`` file; or a directory holding a ``best.pth`` --, run ``InferenceEpocher``
         over the test loader (loss, Dice, Hausdorff distance; PNGs of image, label and prediction under ``save_dir``) and
@@ -126,7 +126,9 @@ class FineTuneTrainer:
         stores list a scan's slices in file-name order, which is z order for the reference's zero-padded names).
         ``postprocess="largest_component"`` adds the ``*_lcc`` meters, ``lcc_removed`` and the ``pred_lcc`` PNGs of the
         prediction reduced to the largest connected component of every foreground class (``InferenceEpocher``); the returned
-        score stays the unprocessed ``DSC_mean``."""
+        score stays the unprocessed ``DSC_mean``.  ``tta="flips"`` / ``"dihedral"`` adds test-time augmentation beside the
+        plain pass: the ``*_tta`` meters, ``tta_entropy``, ``tta_changed`` and the ``pred_tta`` / ``uncertainty_tta`` PNGs of
+        the prediction averaged over the mirrored (and, on square images, transposed) views; the score stays the plain one."""
         if checkpoint is None:
             if not self._save_dir:
                 raise FileNotFoundError("inference(): no checkpoint given and the trainer has no save_dir")
@@ -149,7 +151,7 @@ class FineTuneTrainer:
         self._model.load_state_dict(torch.load(path, map_location="cpu")["_model"])
         evaler = InferenceEpocher(model=self._model, loader=self._test_loader, sup_criterion=self._criterion,
                                   cur_epoch=self._cur_epoch, device=self._device, volumetric=volumetric,
-                                  voxelspacing=voxelspacing, postprocess=postprocess)
+                                  voxelspacing=voxelspacing, postprocess=postprocess, tta=tta)
         evaler.init(save_dir=self._save_dir)
         result = evaler.run()
         return result, evaler.get_score()
