@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 28
+#define SPCL_ABI_VERSION 29
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -751,6 +751,35 @@ int spcl_largest_component(const int64_t* labels, int V, int D, int H, int W, in
 size_t spcl_tta_merge_workspace_bytes(int N, int H, int W);
 int spcl_tta_merge(const float* const* views, const uint8_t* ops, int V, int N, int C, int H, int W, float eps, float* prob,
                    int64_t* pred, float* entropy, float* mean_entropy, void* ws, size_t ws_bytes, void* stream);
+
+/* Pre-training monitor: k-nearest neighbours, label votes, instance retrieval, alignment and uniformity (Wang & Isola 2020)
+ * of N embeddings in one sweep over their N x N similarity matrix, which is never stored (csrc/embed_monitor.hip).  NOT in
+ * the reference; the pre-train trainers opt into it (EmbeddingMonitor, `monitor=`).
+ *   z      [N] rows of d f32, row pitch ldz >= d floats; rows need not be unit length: zh_i = z_i / max(|z_i|, 1e-12) as
+ *          F.normalize (|z_i| from a double sum of squares), s_ij = zh_i . zh_j on the f32 MFMA v_mfma_f32_16x16x4_f32, the
+ *          contraction in one order whatever the position of (i, j): s_ij == s_ji bitwise, equal rows give equal bits.
+ *   labels [L][N] int32 (0 <= L <= 4 kinds; NULL with L == 0);  pair [N] int32: the index of the row's other view, or -1 (a
+ *          value outside [0, N) counts as -1; NULL: no row has one);  1 <= k <= 32.  Labels are only compared with each
+ *          other, never used as an index: the range [0, 65535] the Python binding documents is its contract, not a need
+ *          of the kernel.
+ *   The candidates of row i are all j != i, with exclude_pair also j != pair[i].  Candidate a beats b when s_ia > s_ib, or
+ *   they are equal and a < b.
+ *   knn_idx [N][k] int32, knn_sim [N][k] f32   the k best candidates in rank order; the tail of a row with fewer candidates
+ *                                              is -1 / -inf
+ *   pred    [L][N] int32     the majority label among the row's valid neighbours; equal counts go to the label whose
+ *                            best-ranked neighbour comes first; -1 for a row without a neighbour
+ *   correct [L] int32        the number of rows with pred == label (zeroed by the call's memset)
+ *   pair_rank [N] int32      rows with a pair: the number of j not in {i, pair[i]} that beat pair[i]; else -1
+ *   scalars [4] f64          the mean over paired rows of 2 - 2 s_i,pair (NaN without a paired row) | log of the mean over
+ *                            ordered i != j of exp(-4 (1 - s_ij)) | the number of paired rows | the smallest |z_i|
+ * Limits: 2 <= N <= 8192, 1 <= d <= 512; anything else is SPCL_EINVAL before any launch.  ws: 16-byte aligned,
+ * spcl_embed_monitor_workspace_bytes(N, d, k) bytes (0 outside the limits).  Four launches and, with L > 0, one memset on
+ * `stream`; every floating-point sum in a fixed order (bitwise reproducible), counts by integer atomics; nothing is read
+ * back or allocated: the call can be captured. */
+size_t spcl_embed_monitor_workspace_bytes(int N, int d, int k);
+int spcl_embed_monitor(const float* z, int64_t ldz, const int32_t* labels, int L, const int32_t* pair, int N, int d, int k,
+                       int exclude_pair, int32_t* knn_idx, float* knn_sim, int32_t* pred, int32_t* correct,
+                       int32_t* pair_rank, double* scalars, void* ws, size_t ws_bytes, void* stream);
 
 /* Decoder data movement (NHWC, CS a multiple of 16): nn.Upsample(scale_factor=2) of `_UpConv` (unet.py:89) and its
  * backward (H, W = the low-resolution size in both calls), torch.cat((skip, up), dim=1) (unet.py:194-224) and its

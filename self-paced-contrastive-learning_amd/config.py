@@ -20,3 +20,11 @@ def set_compute_dtype(dtype):
 
 def get_compute_dtype():
     return _compute_dtype
+
+
+def parse_monitor(config):
+    """the ``Monitor`` section of a config (``every``, ``k``, ``max_slices``, ``space``, ``select_by``) -> the dict the
+    pre-train trainers take as ``monitor=``, every key filled in; ``None`` when the section is absent (no monitor: the
+    default).  Unknown keys, values out of range and ``select_by`` keys the monitor cannot produce raise ``ValueError``."""
+    from .semi_seg.epochers.monitor import parse_monitor as _parse
+    return _parse((config or {}).get("Monitor"))

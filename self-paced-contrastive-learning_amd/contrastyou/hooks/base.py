@@ -56,6 +56,11 @@ class CombineTrainerHook(TrainerHook):
     def learnable_modules(self):
         return self._hooks
 
+    @property
+    def hooks(self):
+        """the member trainer hooks, in order"""
+        return list(self._hooks)
+
     def __call__(self):
         return CombineEpochHook(*(hook() for hook in self._hooks))
 

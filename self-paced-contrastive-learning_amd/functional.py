@@ -2,6 +2,7 @@
 no host synchronisation anywhere in this file."""
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 import os
@@ -2919,6 +2920,88 @@ def tta_merge(view_logits, ops, eps=1e-16, want_entropy=True):
             c_float(float(eps)), _n.ptr(prob), _n.ptr(pred), _n.ptr(entropy), _n.ptr(mean_entropy), _n.ptr(ws), ws.numel(),
             _n.stream())
     return prob.permute(0, 3, 1, 2), pred, entropy, mean_entropy
+
+
+# ------------------------------------------------------------------------- pre-training monitor (csrc/embed_monitor.hip)
+EMBED_MONITOR_MAX_N, EMBED_MONITOR_MAX_D, EMBED_MONITOR_MAX_K, EMBED_MONITOR_MAX_KINDS = 8192, 512, 32, 4
+EMBED_MONITOR_MAX_LABEL = 65535
+_EMON_WS = {}  # (device, N, d, k) -> workspace, kept and reused as _SURFACE_WS is (33 MB at the largest shape)
+
+EmbeddingMonitorResult = collections.namedtuple(
+    "EmbeddingMonitorResult", ["knn_idx", "knn_sim", "pred", "correct", "pair_rank", "scalars"])
+
+
+def embedding_monitor(z, labels=None, pair=None, k=20, exclude_pair=True, check_labels=False):
+    """Neighbour statistics of N embeddings in one sweep over their similarity matrix (``spcl_embed_monitor``, four launches,
+    no [N, N] matrix).  ``z`` [N, d] f32 (2 <= N <= 8192, 1 <= d <= 512; rows of any length, normalised as ``F.normalize``);
+    ``labels`` None, an integer [N] vector or [L, N] matrix (or a sequence of [N] vectors) of up to 4 label kinds with values
+    in [0, 65535]; ``pair`` None or an integer [N] vector: the index of the row's other view, or -1; 1 <= ``k`` <= 32.  The
+    candidates of row i are all j != i, with ``exclude_pair`` also j != pair[i]; a larger similarity wins, an equal one goes to
+    the lower index.  -> ``EmbeddingMonitorResult`` of device tensors:
+
+    ``knn_idx`` int32 / ``knn_sim`` f32 [N, k] (rank order; -1 / -inf where a row has fewer candidates), ``pred`` int32 [L, N]
+    (the majority label of the neighbours, equal counts to the label whose best-ranked neighbour comes first, -1 without a
+    neighbour), ``correct`` int32 [L], ``pair_rank`` int32 [N] (how many j outside {i, pair[i]} beat the pair; -1 without a
+    pair) and ``scalars`` f64 [4]: alignment (NaN without a paired row), uniformity, the number of paired rows, the smallest
+    row norm.  Bad arguments raise ``ValueError`` on the host before any device work.  The label range is the interface's
+    contract only -- the kernel compares labels, it never indexes with them --, so it is checked (one read-back) only with
+    ``check_labels=True``.  Nothing else is read back and the call can be captured, but the FIRST call at a shape
+    (device, N, d, k) allocates that shape's workspace, which is kept for every later call: make it outside a capture, or
+    the buffer comes from the graph's private pool."""
+    if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.dtype != torch.float32:
+        raise ValueError("embedding_monitor takes an [N, d] float32 tensor, given "
+                         f"{tuple(z.shape) if isinstance(z, torch.Tensor) else type(z).__name__} {getattr(z, 'dtype', '')}")
+    N, d = z.shape
+    if not 2 <= N <= EMBED_MONITOR_MAX_N or not 1 <= d <= EMBED_MONITOR_MAX_D:
+        raise ValueError(f"embedding_monitor: N = {N} (2 .. {EMBED_MONITOR_MAX_N}), d = {d} (1 .. {EMBED_MONITOR_MAX_D})")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= EMBED_MONITOR_MAX_K:
+        raise ValueError(f"embedding_monitor: k must be an integer in [1, {EMBED_MONITOR_MAX_K}], given {k!r}")
+    if labels is not None and not isinstance(labels, torch.Tensor):
+        labels = list(labels)
+        if any(not isinstance(t, torch.Tensor) or t.dim() != 1 for t in labels):
+            raise ValueError("embedding_monitor: a sequence of labels must hold [N] tensors")
+        labels = torch.stack(labels) if labels else None
+    if labels is not None:
+        if labels.is_floating_point() or labels.dtype == torch.bool or labels.dim() not in (1, 2):
+            raise ValueError(f"embedding_monitor: labels must be an integer [N] or [L, N] tensor, given {tuple(labels.shape)} "
+                             f"{labels.dtype}")
+        labels = labels.view(1, -1) if labels.dim() == 1 else labels
+        if labels.shape[1] != N or labels.shape[0] > EMBED_MONITOR_MAX_KINDS or labels.device != z.device:
+            raise ValueError(f"embedding_monitor: labels of shape {tuple(labels.shape)} on {labels.device} for {N} rows on "
+                             f"{z.device} (at most {EMBED_MONITOR_MAX_KINDS} kinds)")
+        if labels.shape[0] == 0:
+            labels = None
+    if labels is not None and check_labels:
+        lo, hi = int(labels.min()), int(labels.max())
+        if lo < 0 or hi > EMBED_MONITOR_MAX_LABEL:
+            raise ValueError(f"embedding_monitor: labels must lie in [0, {EMBED_MONITOR_MAX_LABEL}], given [{lo}, {hi}]")
+    if pair is not None:
+        if not isinstance(pair, torch.Tensor) or pair.is_floating_point() or pair.dtype == torch.bool or \
+                tuple(pair.shape) != (N,) or pair.device != z.device:
+            raise ValueError(f"embedding_monitor: pair must be an integer [{N}] tensor on {z.device}")
+    _n.require_gpu(z)
+    z = z.detach()
+    if z.stride(1) != 1 or z.stride(0) < d:
+        z = z.contiguous()
+    L = 0 if labels is None else labels.shape[0]
+    lab = None if labels is None else labels.detach().to(torch.int32).contiguous()
+    pr = None if pair is None else pair.detach().to(torch.int32).contiguous()
+    dev = z.device
+    key = (dev, N, d, k)
+    ws = _EMON_WS.get(key)
+    if ws is None:
+        nbytes = _n.call("spcl_embed_monitor_workspace_bytes", N, d, k)
+        ws = _EMON_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    knn_idx = torch.empty((N, k), dtype=torch.int32, device=dev)
+    knn_sim = torch.empty((N, k), dtype=torch.float32, device=dev)
+    pred = torch.empty((L, N), dtype=torch.int32, device=dev)
+    correct = torch.empty((L,), dtype=torch.int32, device=dev)
+    pair_rank = torch.empty((N,), dtype=torch.int32, device=dev)
+    scalars = torch.empty((4,), dtype=torch.float64, device=dev)
+    _n.call("spcl_embed_monitor", _n.ptr(z), z.stride(0), _n.ptr(lab), L, _n.ptr(pr), N, d, k, 1 if exclude_pair else 0,
+            _n.ptr(knn_idx), _n.ptr(knn_sim), _n.ptr(pred) if L else None, _n.ptr(correct) if L else None,
+            _n.ptr(pair_rank), _n.ptr(scalars), _n.ptr(ws), ws.numel(), _n.stream())
+    return EmbeddingMonitorResult(knn_idx, knn_sim, pred, correct, pair_rank, scalars)
 
 
 class _Upsample2xFn(torch.autograd.Function):

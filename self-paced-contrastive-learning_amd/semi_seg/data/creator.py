@@ -211,6 +211,9 @@ class UnlabeledDeviceLoader:
         self._sampler = InfiniteRandomSampler(store, shuffle=shuffle)
         self._out_hw, self._views, self._it = tuple(out_hw), None, None
 
+    views = property(lambda self: self._views, doc="the RecipeViews, built with the first batch (None before it)")
+    out_hw = property(lambda self: self._out_hw, doc="the size training sees")
+
     def __iter__(self):
         self._it = iter(self._sampler)
         return self

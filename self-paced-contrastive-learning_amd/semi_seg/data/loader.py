@@ -44,6 +44,9 @@ class ContrastiveDeviceLoader:
         self._batch_sampler, self._sampler, self._batch_size = batch_sampler, sampler, batch_size
         self._it = None
 
+    views = property(lambda self: self._views, doc="the view generator (RecipeViews, or the legacy PretrainViews)")
+    out_hw = property(lambda self: tuple(self._views.out_hw), doc="the size training sees")
+
     def _index_batches(self):
         if self._batch_sampler is not None:
             yield from iter(self._batch_sampler)

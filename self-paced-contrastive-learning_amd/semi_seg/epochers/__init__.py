@@ -3,3 +3,4 @@ from .finetune import EvalEpocher, FineTuneEpocher, InferenceEpocher  # noqa: F4
 from .legacy import ContrastiveProjectorWrapper, InfoNCEPretrainEpocher  # noqa: F401
 from .semi import SemiSupervisedEpocher  # noqa: F401
 from .adversarial import AdversarialEpocher  # noqa: F401
+from .monitor import EmbeddingMonitor, parse_monitor  # noqa: F401

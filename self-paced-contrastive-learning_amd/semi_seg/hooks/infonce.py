@@ -96,6 +96,11 @@ class INFONCEHook(TrainerHook):
     def is_encoder(self):
         return self._feature_name in encoder_names
 
+    # what the pre-training monitor reads of a contrastive hook
+    feature_name = property(lambda self: self._feature_name)
+    projector = property(lambda self: self._projector)
+    hook_name = property(lambda self: self._hook_name)
+
     def _label_generator(self, *, partition_group, label_group):
         return get_label(self._contrast_on, self._data_name, partition_group, label_group)
 

@@ -43,6 +43,14 @@ def get_label(contrast_on, data_name, partition_group, label_group):
     return global_label_generator(dataset_name=family, contrast_on=contrast_on)(**arguments)
 
 
+def contrast_kinds(data_name):
+    """the ``contrast_on`` values ``get_label`` accepts for a data set, in table order (``NotImplementedError`` for a data set
+    it does not know, as ``get_label``)"""
+    if data_name not in _NAME_RULES:
+        raise NotImplementedError(data_name)
+    return list(_GENERATORS[_NAME_RULES[data_name][0]])
+
+
 def meter_focus(method):
     """run a hook method with the epocher's meters focused on the hook's own group (``self._name``)"""
 

@@ -8,6 +8,7 @@ The reference's RAdam / GradualWarmupScheduler come from the un-vendored ``deepc
 CosineAnnealingLR(T_max=max_epoch-warmup_max, eta_min=1e-7)."""
 import math
 import os
+import warnings
 from typing import Iterable, Optional
 
 import torch
@@ -15,6 +16,8 @@ from torch import nn
 
 from ... import ddp as _ddp
 from ...optim import FusedAdam, FusedAdamW, FusedRAdam, FusedSGD
+from ..epochers.monitor import (LOWER_IS_BETTER, EmbeddingMonitor, expected_keys, monitor_store, parse_monitor,
+                                 resolve_select_by)
 from ..epochers.pretrain import PretrainDecoderEpocher, PretrainEncoderEpocher
 from ..hooks.creator import feature_until_from_hooks
 
@@ -107,7 +110,12 @@ class PretrainEncoderTrainer:
     loader is built from ``unlabeled_loader`` and ``config["ContrastiveLoaderParams"]`` (a missing section raises
     ``RuntimeError`` as the reference does) -- or the mirror's own short form ``chain_dataloader=`` with keyword
     hyper-parameters.  Epoch bookkeeping follows ``new_pretrain.py:69-85``: ``range(max(_cur_epoch + 1, _start_epoch),
-    max_epoch)``, i.e. a fresh trainer runs epochs 1 .. max_epoch - 1 and a resumed one continues after the saved epoch."""
+    max_epoch)``, i.e. a fresh trainer runs epochs 1 .. max_epoch - 1 and a resumed one continues after the saved epoch.
+
+    ``monitor=`` (NOT in the reference; a dict of ``every``, ``k``, ``max_slices``, ``space``, ``select_by``, or the config's
+    ``Monitor`` section): after every ``every``-th epoch the master rank scores the representation on a fixed slice set
+    (``semi_seg/epochers/monitor.py``), keeps the dict under ``history[-1]["monitor"]``, updates ``_best_score`` and writes
+    ``best.pth`` on an improvement.  Absent, the trainer does what it did."""
     RUN_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))),
                             "runs2")
 
@@ -115,7 +123,7 @@ class PretrainEncoderTrainer:
                  unlabeled_loader=None, val_loader=None, test_loader=None, criterion=None, config: Optional[dict] = None,
                  save_dir: Optional[str] = None, max_epoch: int = 80, num_batches: int = 200, device="cuda",
                  lr=None, weight_decay=None, warmup_max=None, multiplier=None, two_stage: bool = False,
-                 disable_bn: bool = False, **kwargs):
+                 disable_bn: bool = False, monitor=None, **kwargs):
         self._model = model
         self._labeled_loader, self._unlabeled_loader = labeled_loader, unlabeled_loader
         self._val_loader, self._test_loader = val_loader, test_loader
@@ -137,7 +145,12 @@ class PretrainEncoderTrainer:
         self.__hooks__ = nn.ModuleList()
         self._inference_until = None
         self._cur_epoch, self._start_epoch, self._best_score = 0, 0, 0
+        self._best_epoch = None  # the epoch of `_best_score` (only the monitor writes either)
         self._optimizer = self._scheduler = self._flat = None
+        # the pre-training monitor (NOT in the reference; semi_seg/epochers/monitor.py): off unless `monitor=` or the config's
+        # `Monitor` section asks for it -- without it nothing below differs from a trainer that has never heard of it
+        self._monitor_cfg = parse_monitor(monitor if monitor is not None else (config or {}).get("Monitor"))
+        self._monitor = self._monitor_indices = self._monitor_key = None
         self.__initialized__ = False
         self.history = []
         if save_dir and config is not None and _ddp.on_master():  # trainer/base.py:40-41 (dump_config)
@@ -184,6 +197,8 @@ class PretrainEncoderTrainer:
 
     # trainer/base.py:44-47,60-83
     def init(self):
+        if self._monitor_cfg is not None:
+            self._resolve_monitor_key()  # (host only, every rank: a `select_by` the hooks cannot produce is refused HERE)
         self._model.to(self._device)
         self.__hooks__.to(self._device)
         _ddp.broadcast_state(self._model, self.__hooks__)
@@ -198,7 +213,41 @@ class PretrainEncoderTrainer:
         self._scheduler = None
         if self._sched_cfg is not None:
             self._scheduler = WarmupCosine(self._optimizer, max_epoch=self._max_epoch, **self._sched_cfg)
+        if self._monitor_cfg is not None and _ddp.on_master():
+            self._build_monitor(self._monitor_indices)
         self.__initialized__ = True
+
+    def _resolve_monitor_key(self):
+        """which key selects best.pth, decided from the registered hooks before anything runs: `select_by` when the monitor
+        can report it (`ValueError` otherwise), by default the first hook's `projection/knn_patient`; `None` when no hook taps
+        an encoder feature (decoder pre-training with dense hooks only) -- the monitor then records `skipped` in the history
+        and leaves `_best_score` and best.pth alone, which a warning says once"""
+        store = monitor_store(self._chain_dataloader)
+        keys = expected_keys(self._model, self.__hooks__, getattr(store, "data_name", "acdc"), self._monitor_cfg["space"])
+        self._monitor_key = resolve_select_by(keys, self._monitor_cfg["select_by"])
+        if self._monitor_key is None:
+            warnings.warn(f"{type(self).__name__}(monitor=...): no contrastive hook taps an encoder feature, so the monitor has "
+                          "nothing to score: it records the skipped hooks and selects no best.pth")
+
+    def _build_monitor(self, indices=None):
+        cfg = self._monitor_cfg
+        self._monitor = EmbeddingMonitor(self._chain_dataloader, max_slices=cfg["max_slices"], k=cfg["k"], space=cfg["space"],
+                                         indices=indices)
+        self._monitor_indices = list(self._monitor.indices)
+
+    def _run_monitor(self):
+        """one evaluation of the fixed slice set: the dict goes into the epoch's history entry, `_best_score` follows
+        `select_by` (the first evaluation always counts), an improvement writes best.pth after last.pth"""
+        result = self._monitor.run(self._model, self.__hooks__)
+        self.history[-1]["monitor"] = result
+        key = self._monitor_key
+        if key is None or key not in result:  # nothing to select by (decided in `init()`; a run never adds to that)
+            return False
+        score = -float(result[key]) if key.rsplit("/", 1)[1] in LOWER_IS_BETTER else float(result[key])
+        improved = self._best_epoch is None or score > self._best_score
+        if improved:
+            self._best_score, self._best_epoch = score, self._cur_epoch
+        return improved
 
     train_epocher = PretrainEncoderEpocher
 
@@ -226,8 +275,15 @@ class PretrainEncoderTrainer:
                 self.history.append(stats)
                 if self._scheduler is not None:
                     self._scheduler.step()
-                if self._save_dir and _ddp.on_master():
-                    self.save_to("last.pth")
+                improved = False
+                try:
+                    if self._monitor is not None and self._cur_epoch % self._monitor_cfg["every"] == 0:
+                        improved = self._run_monitor()
+                finally:  # (whatever the monitor does, the epoch that was just trained is saved)
+                    if self._save_dir and _ddp.on_master():
+                        self.save_to("last.pth")
+                if improved and self._save_dir and _ddp.on_master():
+                    self.save_to("best.pth")
         finally:
             _sg.gc_release()  # (the epochers' captures keep the collector's heap frozen from one epoch to the next)
         return self.history
@@ -239,8 +295,10 @@ class PretrainEncoderTrainer:
                 "__hooks__": self.__hooks__.state_dict(),
                 "_hook_schedulers": [getattr(s, "_scheduler").state_dict() if hasattr(s, "_scheduler") else None
                                      for h in self.__hooks__ for s in getattr(h, "_hooks", [h])],
-                "_buffers": {"_cur_epoch": self._cur_epoch, "_start_epoch": self._start_epoch,
-                             "_best_score": self._best_score}}
+                "_buffers": dict({"_cur_epoch": self._cur_epoch, "_start_epoch": self._start_epoch,
+                                  "_best_score": self._best_score},
+                                 **({"_best_epoch": self._best_epoch, "_monitor_indices": list(self._monitor_indices)}
+                                    if self._monitor is not None else {}))}
 
     def load_state_dict(self, sd):
         self._model.load_state_dict(sd["_model"])
@@ -255,6 +313,13 @@ class PretrainEncoderTrainer:
         self._cur_epoch = sd["_buffers"]["_cur_epoch"]
         self._start_epoch = sd["_buffers"]["_start_epoch"]
         self._best_score = sd["_buffers"].get("_best_score", 0)
+        if self._monitor_cfg is not None:
+            self._best_epoch = sd["_buffers"].get("_best_epoch")
+            saved = sd["_buffers"].get("_monitor_indices")
+            if saved is not None and list(saved) != self._monitor_indices:
+                self._monitor_indices = list(saved)  # the slice set the saved score was measured on
+                if self._monitor is not None:
+                    self._build_monitor(self._monitor_indices)
 
     def save_to(self, save_name=None, name=None):
         name = save_name or name
