@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 29
+#define SPCL_ABI_VERSION 30
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -780,6 +780,31 @@ size_t spcl_embed_monitor_workspace_bytes(int N, int d, int k);
 int spcl_embed_monitor(const float* z, int64_t ldz, const int32_t* labels, int L, const int32_t* pair, int N, int d, int k,
                        int exclude_pair, int32_t* knn_idx, float* knn_sim, int32_t* pred, int32_t* correct,
                        int32_t* pair_rank, double* scalars, void* ws, size_t ws_bytes, void* stream);
+
+/* The same call with groups (ABI 30): group [N] int32, or NULL.  With group[i] >= 0 the candidates of row i also leave out
+ * every j with group[j] == group[i] -- the cells of one scan are near-duplicates of each other, and a vote among them
+ * measures nothing (DenseEmbeddingMonitor, `dense_monitor=`).  A negative id means ungrouped: nothing more is left out for
+ * that row.  The tie rule, uniformity, alignment, pair_rank and the smallest norm are those of spcl_embed_monitor: groups
+ * enter the neighbour lists (knn_idx, knn_sim, pred, correct) and nothing else.  One code path: spcl_embed_monitor IS this call
+ * with group == NULL, bit for bit.  Limits, workspace (spcl_embed_monitor_workspace_bytes), launches, reproducibility and
+ * capture as above; the group ids are read by the sweep where they lie, one per candidate and tile. */
+int spcl_embed_monitor_grouped(const float* z, int64_t ldz, const int32_t* labels, int L, const int32_t* pair,
+                               const int32_t* group, int N, int d, int k, int exclude_pair, int32_t* knn_idx, float* knn_sim,
+                               int32_t* pred, int32_t* correct, int32_t* pair_rank, double* scalars, void* ws, size_t ws_bytes,
+                               void* stream);
+
+/* The majority class of every cell of an adaptive pool (ABI 30): the label of a row of DenseProjectionHead's output.
+ *   labels     [N][H][W] uint8 class codes below C (2 <= C <= 16); a value >= C is counted for no class
+ *   (sh, sw)   the output grid, 1 <= sh <= H, 1 <= sw <= W.  Cell (u, v) covers rows floor(u H / sh) .. ceil((u + 1) H / sh) - 1
+ *              and the same rule for columns: the windows of nn.AdaptiveAvgPool2d, which overlap when the size does not divide
+ *   cell_label [N][sh][sw] int32   the class with the largest integer count in the window, equal counts to the lower class;
+ *                                  -1 for a window that holds only values >= C
+ *   purity     [N][sh][sw] f32, may be NULL   float(count) / float(window size), correctly rounded; 0 with label -1
+ * H, W <= 32768, N sh sw < 2^31 - 4; anything else is SPCL_EINVAL before the launch.  One launch on `stream`, one wave per
+ * cell, integer counts from ballots (no atomics, no floating-point sum): the same bits every run; nothing is read back or
+ * allocated: the call can be captured. */
+int spcl_cell_majority(const uint8_t* labels, int N, int H, int W, int C, int sh, int sw, int32_t* cell_label, float* purity,
+                       void* stream);
 
 /* Decoder data movement (NHWC, CS a multiple of 16): nn.Upsample(scale_factor=2) of `_UpConv` (unet.py:89) and its
  * backward (H, W = the low-resolution size in both calls), torch.cat((skip, up), dim=1) (unet.py:194-224) and its

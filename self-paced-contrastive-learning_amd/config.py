@@ -28,3 +28,11 @@ def parse_monitor(config):
     default).  Unknown keys, values out of range and ``select_by`` keys the monitor cannot produce raise ``ValueError``."""
     from .semi_seg.epochers.monitor import parse_monitor as _parse
     return _parse((config or {}).get("Monitor"))
+
+
+def parse_dense_monitor(config):
+    """the ``DenseMonitor`` section of a config (``every``, ``k``, ``max_slices``, ``space``, ``exclude``, ``select_by``) -> the
+    dict the pre-train trainers take as ``dense_monitor=``, every key filled in; ``None`` when the section is absent (no dense
+    monitor: the default).  Unknown keys and bad values raise ``ValueError``."""
+    from .semi_seg.epochers.dense_monitor import parse_dense_monitor as _parse
+    return _parse((config or {}).get("DenseMonitor"))

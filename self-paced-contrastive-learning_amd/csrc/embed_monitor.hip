@@ -6,6 +6,9 @@
 //   knn         the k candidates no other candidate beats, in that order
 //   pred        the majority label among them; equal counts go to the label whose best-ranked neighbour comes first
 //   pair_rank   the number of j not in {i, pair[i]} that beat pair[i]
+// spcl_embed_monitor_grouped: with group[i] >= 0 the candidates of row i also leave out every j with group[j] == group[i]
+// (a scan's cells are near-duplicates of each other); the groups enter the neighbour lists and nothing else.  The sweep tests
+// one more predicate per candidate; spcl_embed_monitor is the same code with group == NULL.
 //   alignment   the mean over paired rows of 2 - 2 s_i,pair;  uniformity  log mean_{i != j} exp(-4 (1 - s_ij))
 //
 // Four launches and (L > 0) one memset of `correct`:
@@ -160,6 +163,7 @@ struct EmonSweep {
   const float* zh;
   const int32_t* pair;
   const float* spair;
+  const int32_t* group;  // [N] or NULL (spcl_embed_monitor): rows of one non-negative id are no candidates of each other
   float* pl_s;
   int* pl_j;
   int* prank;
@@ -182,6 +186,11 @@ __global__ __launch_bounds__(256) void emon_sweep_kernel(EmonSweep a) {
     prow[threadIdx.x] = i < a.N ? emon_pair_of(a.pair, i, a.N) : -1;
     sprow[threadIdx.x] = a.spair[i];
   }
+  // the group id of row 16 w + (lane & 15): row R's id is one readlane away (an SGPR).  A row that leaves no group out
+  // (a negative id, no group vector) holds INT_MIN, which no column holds -- theirs are clamped to >= -1 --, so that the
+  // whole rule is ONE comparison per candidate
+  int grow = (a.group != nullptr && I0 + 16 * w + r16 < a.N) ? a.group[I0 + 16 * w + r16] : -1;
+  grow = grow < 0 ? INT_MIN : grow;
   float ls[16];  // entry `lane` of the top-k list of row 16 w + R
   int lj[16];
 #pragma unroll
@@ -197,6 +206,9 @@ __global__ __launch_bounds__(256) void emon_sweep_kernel(EmonSweep a) {
     f32x4 acc[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // the group id of the tile's column `lane`, asked for with the tile: one value per lane, as the candidate is, and here
+    // before the products (a copy in LDS read after them costs the kernel 17 VGPRs and its third wave per SIMD)
+    const int gj = (a.group != nullptr && J0 + lane < a.N) ? max(a.group[J0 + lane], -1) : -1;
     for (int kc = 0; kc < a.DP; kc += 64) {
       emon_stage<false>(As, a.zh, a.DP, I0, nullptr, kc);
       emon_stage<false>(Bs, a.zh, a.DP, J0, nullptr, kc);
@@ -218,7 +230,9 @@ __global__ __launch_bounds__(256) void emon_sweep_kernel(EmonSweep a) {
       const float s = Ss[(16 * w + R) * EMON_SP + lane];
       const int p = prow[16 * w + R];
       const float sp = sprow[16 * w + R];
+      const int gi = __builtin_amdgcn_readlane(grow, R);
       const bool real = j < a.N && j != i;
+      const bool cand = gj != gi;  // (groups enter the neighbour lists only: not uniformity, not pair_rank)
       us += real ? (double)expf(fmaf(4.f, s, -4.f)) : 0.0;
       const bool notp = j != p;
       if (p >= 0) {
@@ -227,7 +241,7 @@ __global__ __launch_bounds__(256) void emon_sweep_kernel(EmonSweep a) {
       }
       const float ks = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ls[R]), klast));
       const int kj = __builtin_amdgcn_readlane(lj[R], klast);
-      unsigned long long m = __ballot(real && (notp || !a.excl) && emon_beats(s, j, ks, kj));
+      unsigned long long m = __ballot(real && (notp || !a.excl) && cand && emon_beats(s, j, ks, kj));
       while (m != 0) {  // (uniform) the candidates that beat the k-th entry as it stood, in column order
         const int src = __builtin_ctzll(m);
         m &= m - 1;
@@ -411,6 +425,46 @@ __global__ __launch_bounds__(64 * EMON_CLOSE_ROWS) void emon_close_kernel(EmonCl
   }
 }
 
+// ------------------------------------------------------------------------------------------------ the label of a pooled cell
+// spcl_cell_majority: the majority class of every window of nn.AdaptiveAvgPool2d((sh, sw)) over uint8 label maps -- the label
+// of a row of DenseProjectionHead's output.  One wave per cell: 64 pixels of the window at a time, a class's count grows by the
+// popcount of one ballot, so the C counts are wave-uniform integers (no atomics, no floating-point sum, the same bits every run).
+constexpr int CMAJ_MAX_C = 16, CMAJ_MAX_HW = 32768;  // ((u + 1) H + sh - 1 <= H^2 + H stays an int)
+
+__global__ __launch_bounds__(256) void cmaj_kernel(const uint8_t* __restrict__ labels, int cells, int H, int W, int C, int sh,
+                                                  int sw, int32_t* __restrict__ cell_label, float* __restrict__ purity) {
+  const int lane = threadIdx.x & 63, cell = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (cell >= cells) return;  // (uniform in the wave)
+  const int v = cell % sw, u = (cell / sw) % sh, n = cell / (sw * sh);
+  const int r0 = (u * H) / sh, r1 = ((u + 1) * H + sh - 1) / sh, c0 = (v * W) / sw, c1 = ((v + 1) * W + sw - 1) / sw;
+  const int ww = c1 - c0, size = (r1 - r0) * ww;  // rows r0 .. r1 - 1, columns c0 .. c1 - 1, all inside the map
+  const uint8_t* src = labels + (size_t)n * H * W;
+  int cnt[CMAJ_MAX_C];
+#pragma unroll
+  for (int c = 0; c < CMAJ_MAX_C; ++c) cnt[c] = 0;
+  for (int e0 = 0; e0 < size; e0 += 64) {
+    const int e = e0 + lane;
+    int val = 255;  // (a lane past the window: counted for no class, as every value >= C is)
+    if (e < size) {
+      const int r = e / ww;
+      val = src[(size_t)(r0 + r) * W + c0 + (e - r * ww)];
+    }
+#pragma unroll
+    for (int c = 0; c < CMAJ_MAX_C; ++c) cnt[c] += __popcll(__ballot(val == c));
+  }
+  int best = -1, most = 0;
+#pragma unroll
+  for (int c = 0; c < CMAJ_MAX_C; ++c)
+    if (c < C && cnt[c] > most) {  // (strict: equal counts stay with the lower class)
+      most = cnt[c];
+      best = c;
+    }
+  if (lane == 0) {
+    cell_label[cell] = best;
+    if (purity != nullptr) purity[cell] = __fdiv_rn((float)most, (float)size);
+  }
+}
+
 }  // namespace spcl
 
 using namespace spcl;
@@ -424,35 +478,67 @@ extern "C" size_t spcl_embed_monitor_workspace_bytes(int N, int d, int k) {
   return emon_ws(nullptr, N, d, k).bytes;
 }
 
-extern "C" int spcl_embed_monitor(const float* z, int64_t ldz, const int32_t* labels, int L, const int32_t* pair, int N, int d,
-                                  int k, int exclude_pair, int32_t* knn_idx, float* knn_sim, int32_t* pred,
-                                  int32_t* correct, int32_t* pair_rank, double* scalars, void* ws, size_t ws_bytes,
-                                  void* stream) {
-  SPCL_CHECK_ARG(emon_shape_ok(N, d, k), "spcl_embed_monitor: N = %d (2 .. %d), d = %d (1 .. %d), k = %d (1 .. %d)", N,
+// the one code path of both entries: `what` names the entry in the messages, `group` is NULL for spcl_embed_monitor
+static int emon_run(const char* what, const float* z, int64_t ldz, const int32_t* labels, int L, const int32_t* pair,
+                    const int32_t* group, int N, int d, int k, int exclude_pair, int32_t* knn_idx, float* knn_sim, int32_t* pred,
+                    int32_t* correct, int32_t* pair_rank, double* scalars, void* ws, size_t ws_bytes, void* stream) {
+  SPCL_CHECK_ARG(emon_shape_ok(N, d, k), "%s: N = %d (2 .. %d), d = %d (1 .. %d), k = %d (1 .. %d)", what, N,
                  EMON_MAX_N, d, EMON_MAX_D, k, EMON_MAX_K);
-  SPCL_CHECK_ARG(L >= 0 && L <= EMON_MAX_L, "spcl_embed_monitor: L = %d label kinds (0 .. %d)", L, EMON_MAX_L);
-  SPCL_CHECK_ARG(ldz >= d, "spcl_embed_monitor: row pitch %ld below d = %d", (long)ldz, d);
-  SPCL_CHECK_ARG(z && knn_idx && knn_sim && pair_rank && scalars && ws, "spcl_embed_monitor: null pointer");
-  SPCL_CHECK_ARG(L == 0 || (labels && pred && correct), "spcl_embed_monitor: null pointer (labels, pred or correct with L = %d)",
+  SPCL_CHECK_ARG(L >= 0 && L <= EMON_MAX_L, "%s: L = %d label kinds (0 .. %d)", what, L, EMON_MAX_L);
+  SPCL_CHECK_ARG(ldz >= d, "%s: row pitch %ld below d = %d", what, (long)ldz, d);
+  SPCL_CHECK_ARG(z && knn_idx && knn_sim && pair_rank && scalars && ws, "%s: null pointer", what);
+  SPCL_CHECK_ARG(L == 0 || (labels && pred && correct), "%s: null pointer (labels, pred or correct with L = %d)", what,
                  L);
-  SPCL_CHECK_ARG((uintptr_t)ws % 16 == 0 && (uintptr_t)scalars % 8 == 0, "spcl_embed_monitor: misaligned workspace or scalars");
+  SPCL_CHECK_ARG((uintptr_t)ws % 16 == 0 && (uintptr_t)scalars % 8 == 0, "%s: misaligned workspace or scalars", what);
   const EmonWs w = emon_ws(ws, N, d, k);
-  SPCL_CHECK_ARG(ws_bytes >= w.bytes, "spcl_embed_monitor: workspace of %zu bytes, %zu needed", ws_bytes, w.bytes);
+  SPCL_CHECK_ARG(ws_bytes >= w.bytes, "%s: workspace of %zu bytes, %zu needed", what, ws_bytes, w.bytes);
   hipStream_t st = (hipStream_t)stream;
   const int NP = round_up(N, 64), DP = round_up(d, 64), RB = NP / 64, CS = emon_split(N);
   if (L > 0 && hipMemsetAsync(correct, 0, (size_t)L * sizeof(int32_t), st) != hipSuccess) {
     (void)hipGetLastError();
-    set_error("spcl_embed_monitor: memset failed");
+    set_error("%s: memset failed", what);
     return SPCL_ELAUNCH;
   }
   SPCL_LAUNCH(emon_norm_kernel, dim3(NP / 4), dim3(256), 0, st, z, ldz, N, d, DP, w.zh, w.norm);
   SPCL_LAUNCH(emon_pair_kernel, dim3(RB), dim3(256), 0, st, (const float*)w.zh, DP, N, pair, w.spair);
-  const EmonSweep sw{w.zh, pair, w.spair, w.pl_s, w.pl_j, w.prank, w.usum, N, NP, DP, k, exclude_pair ? 1 : 0, cdiv(RB, CS)};
+  const EmonSweep sw{w.zh, pair, w.spair, group, w.pl_s, w.pl_j, w.prank, w.usum, N, NP, DP, k, exclude_pair ? 1 : 0, cdiv(RB, CS)};
   prof_cost((double)RB * NP * DP * 8.0, 2.0 * NP * NP * DP);
   SPCL_LAUNCH(emon_sweep_kernel, dim3(RB, CS), dim3(256), 0, st, sw);
   const EmonClose cl{w.pl_s, w.pl_j, w.prank, w.usum, w.norm, w.spair, pair, labels, N, NP, k, L, CS, RB * CS,
                      knn_idx, knn_sim, pred, correct, pair_rank, scalars};
   SPCL_LAUNCH(emon_close_kernel, dim3(cdiv(N, EMON_CLOSE_ROWS)), dim3(64 * EMON_CLOSE_ROWS), 0, st, cl);
-  SPCL_LAUNCH_CHECK("spcl_embed_monitor");
+  SPCL_LAUNCH_CHECK(what);
+  return SPCL_OK;
+}
+
+extern "C" int spcl_embed_monitor(const float* z, int64_t ldz, const int32_t* labels, int L, const int32_t* pair, int N, int d,
+                                  int k, int exclude_pair, int32_t* knn_idx, float* knn_sim, int32_t* pred,
+                                  int32_t* correct, int32_t* pair_rank, double* scalars, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  return emon_run("spcl_embed_monitor", z, ldz, labels, L, pair, nullptr, N, d, k, exclude_pair, knn_idx, knn_sim, pred, correct,
+                  pair_rank, scalars, ws, ws_bytes, stream);
+}
+
+// (the workspace is that of spcl_embed_monitor: the group ids are read where they lie)
+extern "C" int spcl_embed_monitor_grouped(const float* z, int64_t ldz, const int32_t* labels, int L, const int32_t* pair,
+                                          const int32_t* group, int N, int d, int k, int exclude_pair, int32_t* knn_idx,
+                                          float* knn_sim, int32_t* pred, int32_t* correct, int32_t* pair_rank, double* scalars,
+                                          void* ws, size_t ws_bytes, void* stream) {
+  return emon_run("spcl_embed_monitor_grouped", z, ldz, labels, L, pair, group, N, d, k, exclude_pair, knn_idx, knn_sim, pred,
+                  correct, pair_rank, scalars, ws, ws_bytes, stream);
+}
+
+extern "C" int spcl_cell_majority(const uint8_t* labels, int N, int H, int W, int C, int sh, int sw, int32_t* cell_label,
+                                  float* purity, void* stream) {
+  SPCL_CHECK_ARG(N >= 1 && H >= 1 && W >= 1 && H <= CMAJ_MAX_HW && W <= CMAJ_MAX_HW,
+                 "spcl_cell_majority: N = %d (>= 1), H = %d, W = %d (1 .. %d)", N, H, W, CMAJ_MAX_HW);
+  SPCL_CHECK_ARG(C >= 2 && C <= CMAJ_MAX_C, "spcl_cell_majority: C = %d classes (2 .. %d)", C, CMAJ_MAX_C);
+  SPCL_CHECK_ARG(sh >= 1 && sh <= H && sw >= 1 && sw <= W, "spcl_cell_majority: grid %d x %d for maps of %d x %d", sh, sw, H, W);
+  SPCL_CHECK_ARG((int64_t)N * sh * sw <= INT_MAX - 4, "spcl_cell_majority: %d x %d x %d cells (at most 2^31 - 5)", N, sh, sw);
+  SPCL_CHECK_ARG(labels && cell_label, "spcl_cell_majority: null pointer");
+  const int cells = N * sh * sw;
+  SPCL_LAUNCH(cmaj_kernel, dim3(cdiv(cells, 4)), dim3(256), 0, (hipStream_t)stream, labels, cells, H, W, C, sh, sw, cell_label,
+              purity);
+  SPCL_LAUNCH_CHECK("spcl_cell_majority");
   return SPCL_OK;
 }

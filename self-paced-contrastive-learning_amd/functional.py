@@ -2931,7 +2931,7 @@ EmbeddingMonitorResult = collections.namedtuple(
     "EmbeddingMonitorResult", ["knn_idx", "knn_sim", "pred", "correct", "pair_rank", "scalars"])
 
 
-def embedding_monitor(z, labels=None, pair=None, k=20, exclude_pair=True, check_labels=False):
+def embedding_monitor(z, labels=None, pair=None, k=20, exclude_pair=True, check_labels=False, *, group=None):
     """Neighbour statistics of N embeddings in one sweep over their similarity matrix (``spcl_embed_monitor``, four launches,
     no [N, N] matrix).  ``z`` [N, d] f32 (2 <= N <= 8192, 1 <= d <= 512; rows of any length, normalised as ``F.normalize``);
     ``labels`` None, an integer [N] vector or [L, N] matrix (or a sequence of [N] vectors) of up to 4 label kinds with values
@@ -2947,7 +2947,11 @@ def embedding_monitor(z, labels=None, pair=None, k=20, exclude_pair=True, check_
     contract only -- the kernel compares labels, it never indexes with them --, so it is checked (one read-back) only with
     ``check_labels=True``.  Nothing else is read back and the call can be captured, but the FIRST call at a shape
     (device, N, d, k) allocates that shape's workspace, which is kept for every later call: make it outside a capture, or
-    the buffer comes from the graph's private pool."""
+    the buffer comes from the graph's private pool.
+
+    ``group`` (keyword only) None or an integer [N] vector on z's device: with ``group[i] >= 0`` the candidates of row i also
+    leave out every j with ``group[j] == group[i]`` (``spcl_embed_monitor_grouped``; a negative id: ungrouped, nothing more is
+    left out).  Groups enter ``knn_idx`` / ``knn_sim`` / ``pred`` / ``correct`` only.  ``group=None`` is the call it always was."""
     if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.dtype != torch.float32:
         raise ValueError("embedding_monitor takes an [N, d] float32 tensor, given "
                          f"{tuple(z.shape) if isinstance(z, torch.Tensor) else type(z).__name__} {getattr(z, 'dtype', '')}")
@@ -2979,6 +2983,10 @@ def embedding_monitor(z, labels=None, pair=None, k=20, exclude_pair=True, check_
         if not isinstance(pair, torch.Tensor) or pair.is_floating_point() or pair.dtype == torch.bool or \
                 tuple(pair.shape) != (N,) or pair.device != z.device:
             raise ValueError(f"embedding_monitor: pair must be an integer [{N}] tensor on {z.device}")
+    if group is not None:
+        if not isinstance(group, torch.Tensor) or group.is_floating_point() or group.dtype == torch.bool or \
+                tuple(group.shape) != (N,) or group.device != z.device:
+            raise ValueError(f"embedding_monitor: group must be an integer [{N}] tensor on {z.device}")
     _n.require_gpu(z)
     z = z.detach()
     if z.stride(1) != 1 or z.stride(0) < d:
@@ -2998,10 +3006,48 @@ def embedding_monitor(z, labels=None, pair=None, k=20, exclude_pair=True, check_
     correct = torch.empty((L,), dtype=torch.int32, device=dev)
     pair_rank = torch.empty((N,), dtype=torch.int32, device=dev)
     scalars = torch.empty((4,), dtype=torch.float64, device=dev)
-    _n.call("spcl_embed_monitor", _n.ptr(z), z.stride(0), _n.ptr(lab), L, _n.ptr(pr), N, d, k, 1 if exclude_pair else 0,
-            _n.ptr(knn_idx), _n.ptr(knn_sim), _n.ptr(pred) if L else None, _n.ptr(correct) if L else None,
+    outs = (_n.ptr(knn_idx), _n.ptr(knn_sim), _n.ptr(pred) if L else None, _n.ptr(correct) if L else None,
             _n.ptr(pair_rank), _n.ptr(scalars), _n.ptr(ws), ws.numel(), _n.stream())
+    if group is None:
+        _n.call("spcl_embed_monitor", _n.ptr(z), z.stride(0), _n.ptr(lab), L, _n.ptr(pr), N, d, k, 1 if exclude_pair else 0,
+                *outs)
+    else:
+        gr = group.detach().to(torch.int32).contiguous()
+        _n.call("spcl_embed_monitor_grouped", _n.ptr(z), z.stride(0), _n.ptr(lab), L, _n.ptr(pr), _n.ptr(gr), N, d, k,
+                1 if exclude_pair else 0, *outs)
     return EmbeddingMonitorResult(knn_idx, knn_sim, pred, correct, pair_rank, scalars)
+
+
+CELL_MAJORITY_MAX_C = 16
+
+
+def cell_majority(labels, C, size, purity=True):
+    """The label of every cell of an adaptive pool (``spcl_cell_majority``, one launch, integer counts): ``labels`` [N, H, W]
+    (or [N, 1, H, W]) uint8 class codes below ``C`` (2 .. 16), ``size`` = (sh, sw) with 1 <= sh <= H, 1 <= sw <= W.  Cell
+    (u, v) is the window of ``nn.AdaptiveAvgPool2d(size)``.  -> (``cell_label`` int32 [N, sh, sw]: the class with the largest
+    count, equal counts to the lower class, -1 for a window of values >= C only; ``purity`` f32 [N, sh, sw]: count / window
+    size, or None with ``purity=False``).  Bad arguments raise ``ValueError`` on the host; nothing is read back."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8:
+        raise ValueError("cell_majority takes uint8 label maps, given "
+                         f"{getattr(labels, 'dtype', type(labels).__name__)}")
+    if labels.dim() == 4 and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    if labels.dim() != 3 or min(labels.shape) < 1:
+        raise ValueError(f"cell_majority: label maps must be [N, H, W] or [N, 1, H, W], given {tuple(labels.shape)}")
+    if isinstance(C, bool) or not isinstance(C, int) or not 2 <= C <= CELL_MAJORITY_MAX_C:
+        raise ValueError(f"cell_majority: C must be an integer in [2, {CELL_MAJORITY_MAX_C}], given {C!r}")
+    size = (size, size) if isinstance(size, int) and not isinstance(size, bool) else tuple(size)
+    N, H, W = labels.shape
+    if len(size) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in size) or \
+            not 1 <= size[0] <= H or not 1 <= size[1] <= W:
+        raise ValueError(f"cell_majority: grid {size} for maps of {H} x {W} (1 <= sh <= H, 1 <= sw <= W)")
+    sh, sw = size
+    _n.require_gpu(labels)
+    labels = labels.detach().contiguous()
+    cell = torch.empty((N, sh, sw), dtype=torch.int32, device=labels.device)
+    pur = torch.empty((N, sh, sw), dtype=torch.float32, device=labels.device) if purity else None
+    _n.call("spcl_cell_majority", _n.ptr(labels), N, H, W, C, sh, sw, _n.ptr(cell), _n.ptr(pur), _n.stream())
+    return cell, pur
 
 
 class _Upsample2xFn(torch.autograd.Function):

@@ -4,3 +4,4 @@ from .legacy import ContrastiveProjectorWrapper, InfoNCEPretrainEpocher  # noqa:
 from .semi import SemiSupervisedEpocher  # noqa: F401
 from .adversarial import AdversarialEpocher  # noqa: F401
 from .monitor import EmbeddingMonitor, parse_monitor  # noqa: F401
+from .dense_monitor import DenseEmbeddingMonitor, parse_dense_monitor  # noqa: F401

@@ -16,6 +16,7 @@ from torch import nn
 
 from ... import ddp as _ddp
 from ...optim import FusedAdam, FusedAdamW, FusedRAdam, FusedSGD
+from ..epochers import dense_monitor as _dense
 from ..epochers.monitor import (LOWER_IS_BETTER, EmbeddingMonitor, expected_keys, monitor_store, parse_monitor,
                                  resolve_select_by)
 from ..epochers.pretrain import PretrainDecoderEpocher, PretrainEncoderEpocher
@@ -115,7 +116,14 @@ class PretrainEncoderTrainer:
     ``monitor=`` (NOT in the reference; a dict of ``every``, ``k``, ``max_slices``, ``space``, ``select_by``, or the config's
     ``Monitor`` section): after every ``every``-th epoch the master rank scores the representation on a fixed slice set
     (``semi_seg/epochers/monitor.py``), keeps the dict under ``history[-1]["monitor"]``, updates ``_best_score`` and writes
-    ``best.pth`` on an improvement.  Absent, the trainer does what it did."""
+    ``best.pth`` on an improvement.  Absent, the trainer does what it did.
+
+    ``dense_monitor=`` (NOT in the reference; a dict of ``every``, ``k``, ``max_slices``, ``space``, ``exclude``, ``select_by``,
+    or the config's ``DenseMonitor`` section): the same for the contrastive hooks on DECODER features, which ``monitor=`` only
+    names in ``skipped`` -- leave-one-scan-out k-NN classification of the pooled cells against the store's label maps
+    (``semi_seg/epochers/dense_monitor.py``) into ``history[-1]["dense_monitor"]``, ``_best_score`` and ``best.pth``.  One run
+    selects by one key: a run in which both monitors resolve a selection key is refused in ``init()``
+    (``DenseMonitor.select_by: false`` records without selecting)."""
     RUN_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))),
                             "runs2")
 
@@ -123,7 +131,7 @@ class PretrainEncoderTrainer:
                  unlabeled_loader=None, val_loader=None, test_loader=None, criterion=None, config: Optional[dict] = None,
                  save_dir: Optional[str] = None, max_epoch: int = 80, num_batches: int = 200, device="cuda",
                  lr=None, weight_decay=None, warmup_max=None, multiplier=None, two_stage: bool = False,
-                 disable_bn: bool = False, monitor=None, **kwargs):
+                 disable_bn: bool = False, monitor=None, dense_monitor=None, **kwargs):
         self._model = model
         self._labeled_loader, self._unlabeled_loader = labeled_loader, unlabeled_loader
         self._val_loader, self._test_loader = val_loader, test_loader
@@ -151,6 +159,10 @@ class PretrainEncoderTrainer:
         # `Monitor` section asks for it -- without it nothing below differs from a trainer that has never heard of it
         self._monitor_cfg = parse_monitor(monitor if monitor is not None else (config or {}).get("Monitor"))
         self._monitor = self._monitor_indices = self._monitor_key = None
+        # the dense monitor (semi_seg/epochers/dense_monitor.py): off unless `dense_monitor=` or the `DenseMonitor` section
+        self._dense_cfg = _dense.parse_dense_monitor(
+            dense_monitor if dense_monitor is not None else (config or {}).get("DenseMonitor"))
+        self._dense_monitor = self._dense_indices = self._dense_key = None
         self.__initialized__ = False
         self.history = []
         if save_dir and config is not None and _ddp.on_master():  # trainer/base.py:40-41 (dump_config)
@@ -199,6 +211,8 @@ class PretrainEncoderTrainer:
     def init(self):
         if self._monitor_cfg is not None:
             self._resolve_monitor_key()  # (host only, every rank: a `select_by` the hooks cannot produce is refused HERE)
+        if self._dense_cfg is not None:
+            self._resolve_dense_key()  # (host only, every rank; after the monitor's: one run selects by one key)
         self._model.to(self._device)
         self.__hooks__.to(self._device)
         _ddp.broadcast_state(self._model, self.__hooks__)
@@ -215,6 +229,8 @@ class PretrainEncoderTrainer:
             self._scheduler = WarmupCosine(self._optimizer, max_epoch=self._max_epoch, **self._sched_cfg)
         if self._monitor_cfg is not None and _ddp.on_master():
             self._build_monitor(self._monitor_indices)
+        if self._dense_cfg is not None and _ddp.on_master():
+            self._build_dense_monitor(self._dense_indices)
         self.__initialized__ = True
 
     def _resolve_monitor_key(self):
@@ -244,6 +260,43 @@ class PretrainEncoderTrainer:
         if key is None or key not in result:  # nothing to select by (decided in `init()`; a run never adds to that)
             return False
         score = -float(result[key]) if key.rsplit("/", 1)[1] in LOWER_IS_BETTER else float(result[key])
+        improved = self._best_epoch is None or score > self._best_score
+        if improved:
+            self._best_score, self._best_epoch = score, self._cur_epoch
+        return improved
+
+    def _resolve_dense_key(self):
+        """the dense monitor's part of `init()`, host only: no contrastive hook on a decoder feature, a store without label
+        maps, a `select_by` the hooks cannot produce, and a second selector beside the monitor's are each a `ValueError`"""
+        name = type(self).__name__
+        if not _dense.dense_targets(self.__hooks__):
+            raise ValueError(f"{name}(dense_monitor=...): no contrastive hook taps a decoder feature, the dense monitor has "
+                             "nothing to score (hooks on encoder features are the business of `monitor=`)")
+        if getattr(monitor_store(self._chain_dataloader), "targets", None) is None:
+            raise ValueError(f"{name}(dense_monitor=...): the pre-training store has no label maps (`targets`), and the dense "
+                             "monitor votes on the classes of its `val` views")
+        keys = _dense.expected_keys(self._model, self.__hooks__, self._dense_cfg["space"])
+        self._dense_key = _dense.resolve_select_by(keys, self._dense_cfg["select_by"])
+        if self._dense_key is not None and self._monitor_key is not None:
+            raise ValueError(f"{name}: two selectors for one best.pth -- Monitor selects by {self._monitor_key!r} and DenseMonitor "
+                             f"by {self._dense_key!r}; one run selects by one key (`DenseMonitor.select_by: false` records "
+                             "without selecting, or leave `Monitor` out)")
+
+    def _build_dense_monitor(self, indices=None):
+        cfg = self._dense_cfg
+        self._dense_monitor = _dense.DenseEmbeddingMonitor(
+            self._chain_dataloader, self.__hooks__, max_slices=cfg["max_slices"], k=cfg["k"], space=cfg["space"],
+            exclude=cfg["exclude"], indices=indices)
+        self._dense_indices = list(self._dense_monitor.indices)
+
+    def _run_dense_monitor(self):
+        """as `_run_monitor`, into `history[-1]["dense_monitor"]`"""
+        result = self._dense_monitor.run(self._model, self.__hooks__)
+        self.history[-1]["dense_monitor"] = result
+        key = self._dense_key
+        if key is None or key not in result:
+            return False
+        score = -float(result[key]) if key.rsplit("/", 1)[1] in _dense.DENSE_LOWER_IS_BETTER else float(result[key])
         improved = self._best_epoch is None or score > self._best_score
         if improved:
             self._best_score, self._best_epoch = score, self._cur_epoch
@@ -279,6 +332,8 @@ class PretrainEncoderTrainer:
                 try:
                     if self._monitor is not None and self._cur_epoch % self._monitor_cfg["every"] == 0:
                         improved = self._run_monitor()
+                    if self._dense_monitor is not None and self._cur_epoch % self._dense_cfg["every"] == 0:
+                        improved = self._run_dense_monitor() or improved
                 finally:  # (whatever the monitor does, the epoch that was just trained is saved)
                     if self._save_dir and _ddp.on_master():
                         self.save_to("last.pth")
@@ -298,7 +353,11 @@ class PretrainEncoderTrainer:
                 "_buffers": dict({"_cur_epoch": self._cur_epoch, "_start_epoch": self._start_epoch,
                                   "_best_score": self._best_score},
                                  **({"_best_epoch": self._best_epoch, "_monitor_indices": list(self._monitor_indices)}
-                                    if self._monitor is not None else {}))}
+                                    if self._monitor is not None else {}),
+                                 **({"_dense_monitor_indices": list(self._dense_indices)}
+                                    if self._dense_monitor is not None else {}),
+                                 **({"_best_epoch": self._best_epoch}
+                                    if self._dense_monitor is not None and self._monitor is None else {}))}
 
     def load_state_dict(self, sd):
         self._model.load_state_dict(sd["_model"])
@@ -320,6 +379,13 @@ class PretrainEncoderTrainer:
                 self._monitor_indices = list(saved)  # the slice set the saved score was measured on
                 if self._monitor is not None:
                     self._build_monitor(self._monitor_indices)
+        if self._dense_cfg is not None:
+            self._best_epoch = sd["_buffers"].get("_best_epoch")
+            saved = sd["_buffers"].get("_dense_monitor_indices")
+            if saved is not None and list(saved) != self._dense_indices:
+                self._dense_indices = list(saved)  # the slice set the saved score was measured on
+                if self._dense_monitor is not None:
+                    self._build_dense_monitor(self._dense_indices)
 
     def save_to(self, save_name=None, name=None):
         name = save_name or name
