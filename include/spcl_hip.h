@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 30
+#define SPCL_ABI_VERSION 31
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -1366,6 +1366,36 @@ int spcl_pica_seg_loss(const long long* jacc, const float* jf32, int S, int K, i
 int spcl_pica_global_loss(const float* lx, const float* ly, long ld, int N, int S, int K, float lamda, float scale,
                           const float* gscale, float* loss, float* ce_out, float* dlx, float* dly, void* ws, size_t ws_bytes,
                           void* stream);
+
+/* ---------------------------------------------------------------- soft-Dice + class-weighted KL (csrc/sup_dice.hip) ---
+ * The supervised criterion of contrastyou/losses/dice.py (not in the reference; ABI 31).  p = softmax(logits), t = one-hot of the
+ * label, M = N H W, S = all classes or 1 .. C-1 (include_background == 0), groups g = the batch (G = 1) or one per sample
+ * (per_sample != 0, G = N); I_gc = sum p t, P_gc = sum p, T_gc = sum t over the pixels of group g:
+ *   L_dice = 1 - 1 / (G |S|) sum_g sum_{c in S} (2 I_gc + smooth) / (P_gc + T_gc + smooth)
+ *   L_kl   = 1 / M sum_i class_weight[l_i] * -log((p_{i,l_i} + eps) / (1 + eps))
+ *   loss   = dice_weight L_dice + kl_weight L_kl
+ * A label outside [0, C) is an all-zero one-hot row: no KL term, nothing in I or T, its probabilities count in P.
+ * logits [N][H][W][C] f32 (C <= 16, N <= 1024), labels [N][H][W] int64, class_weight [C] f32, used as given.
+ *
+ *   spcl_sup_dice_forward: two launches (the sums of every workgroup; their fixed-order total).  loss[0], parts[0] = L_kl, parts[1] = L_dice; inter / uni [N][C] int64 = the Dice counts of
+ *                    the arg-max map against the labels, as spcl_sup_loss_forward writes them (written, not added to);
+ *                    coef [G][C][2] f32 = per (group, class) a = -2 / (G |S| D) and b = (2 I + smooth) / (G |S| D^2) with
+ *                    D = P + T + smooth (both 0 outside S): what spcl_sup_dice_backward reads.  Sums in float64 / integers in
+ *                    a fixed order, no floating-point atomics: bitwise reproducible.  ws: spcl_sup_dice_workspace_bytes(N, C,
+ *                    H, W) bytes, 16-byte aligned.  Its first 64 bytes hold the workgroups' ticket: zero them ONCE, when the
+ *                    workspace is allocated -- a call that completes leaves them zero (no memset per call, nothing but the
+ *                    two kernels in a captured graph).  Calls that share a workspace must be ordered on one stream.
+ *   spcl_sup_dice_backward: one launch, no reduction: dlogits [N][H][W][C] = d loss / d logits (times gscale[0] when gscale is
+ *                    non-NULL), with d loss / d p_c = dice_weight (a t_c + b) - [c == l] kl_weight class_weight[l] /
+ *                    (M (p_l + eps)) taken through the softmax. */
+size_t spcl_sup_dice_workspace_bytes(int N, int C, int H, int W);
+int spcl_sup_dice_forward(const float* logits, const int64_t* labels, const float* class_weight, int N, int C, int H, int W,
+                          float dice_weight, float kl_weight, int include_background, int per_sample, float smooth, float eps,
+                          float* loss, float* parts, int64_t* inter, int64_t* uni, float* coef, void* ws, size_t ws_bytes,
+                          void* stream);
+int spcl_sup_dice_backward(const float* logits, const int64_t* labels, const float* class_weight, const float* coef, int N,
+                           int C, int H, int W, float dice_weight, float kl_weight, int per_sample, float eps,
+                           const float* gscale, float* dlogits, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,1 @@
+from .dice import DiceKLLoss, SoftDiceLoss, WeightedKL, build_sup_criterion  # noqa: F401

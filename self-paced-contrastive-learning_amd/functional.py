@@ -2684,6 +2684,69 @@ def sup_loss_kl_onehot(logits, labels, eps=1e-16):
     return loss, counts[0]
 
 
+_SUP_DICE_WS = {}  # (device, stream, N, C, H, W) -> workspace; the calls of one stream on one shape reuse it, in order
+
+
+class _SupDiceFn(torch.autograd.Function):
+    """``dice_weight * soft-Dice + kl_weight * class-weighted KL`` on one-hot targets (csrc/sup_dice.hip,
+    contrastyou/losses/dice.py) + the Dice counts of the arg-max map.  Forward is ONE streaming pass (the sums of every group
+    and class, reduced in a fixed order); the gradient needs those sums, so it is a second pass, launched by ``backward`` --
+    under ``no_grad`` it never runs and nothing is kept.  ``cfg`` = (dice_weight, kl_weight, include_background, per_sample,
+    smooth, eps); ``out`` receives ((inter, union) [N, C] int64, parts [2] = (L_kl, L_dice))."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, cfg, out):
+        _n.require_gpu(logits, labels, weight)
+        ls = _class_map_storage(logits.detach())
+        N, H, W, C = ls.shape
+        lab = labels.detach().long().contiguous()
+        if tuple(lab.shape) != (N, H, W):
+            raise AssertionError(f"labels {tuple(lab.shape)} do not match the class map {(N, H, W)}")
+        dice_weight, kl_weight, include_background, per_sample, smooth, eps = cfg
+        dev = ls.device
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream, N, C, H, W)
+        ws = _SUP_DICE_WS.get(key)
+        if ws is None:  # zeroed once: a call leaves the ticket in its first bytes at zero
+            ws = _SUP_DICE_WS[key] = torch.zeros(max(_n.call("spcl_sup_dice_workspace_bytes", N, C, H, W), 64),
+                                                 dtype=torch.uint8, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        parts = torch.empty(2, dtype=torch.float32, device=dev)  # L_kl, L_dice
+        both = torch.empty(2, N, C, dtype=torch.int64, device=dev)
+        coef = torch.empty(N if per_sample else 1, C, 2, dtype=torch.float32, device=dev)
+        _n.call("spcl_sup_dice_forward", _n.ptr(ls), _n.ptr(lab), _n.ptr(weight), N, C, H, W, c_float(dice_weight),
+                c_float(kl_weight), int(bool(include_background)), int(bool(per_sample)), c_float(smooth), c_float(eps),
+                _n.ptr(loss), _n.ptr(parts), _n.ptr(both[0]), _n.ptr(both[1]), _n.ptr(coef), _n.ptr(ws), ws.numel(),
+                _n.stream())
+        out.append(((both[0], both[1]), parts))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(ls, lab, weight, coef)
+            ctx.cfg = cfg
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        ls, lab, weight, coef = ctx.saved_tensors
+        N, H, W, C = ls.shape
+        dice_weight, kl_weight, _, per_sample, _, eps = ctx.cfg
+        gs = None if is_unit_gradient(g) else g.detach().reshape(1).float().contiguous()  # (scaled inside the one pass)
+        dl = torch.empty_like(ls)
+        _n.call("spcl_sup_dice_backward", _n.ptr(ls), _n.ptr(lab), _n.ptr(weight), _n.ptr(coef), N, C, H, W,
+                c_float(dice_weight), c_float(kl_weight), int(bool(per_sample)), c_float(eps), _n.ptr(gs), _n.ptr(dl),
+                _n.stream())
+        return dl.permute(0, 3, 1, 2), None, None, None, None
+
+
+def sup_dice_kl_onehot(logits, labels, weight, *, dice_weight=1.0, kl_weight=1.0, include_background=True, per_sample=False,
+                       smooth=1e-5, eps=1e-16):
+    """-> (loss, (inter, union), parts): soft-Dice + class-weighted KL of [N,C,H,W] logits against an [N,H,W] label map
+    (``_SupDiceFn``); ``weight`` is a float32 device vector of C class weights, ``parts`` a device [2] tensor (L_kl, L_dice)"""
+    out = []
+    cfg = (float(dice_weight), float(kl_weight), bool(include_background), bool(per_sample), float(smooth), float(eps))
+    loss = _SupDiceFn.apply(logits, labels, weight, cfg, out)
+    counts, parts = out[0]
+    return loss, counts, parts
+
+
 def one_hot_classes(labels: torch.Tensor, K: int) -> torch.Tensor:
     """class2one_hot: [N,H,W] integer labels -> logical [N,K,H,W] f32 one-hot (NHWC storage)."""
     _n.require_gpu(labels)

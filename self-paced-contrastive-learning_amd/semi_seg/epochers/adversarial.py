@@ -15,9 +15,9 @@ from torch import nn
 
 from ... import functional as F_hip
 from ...contrastyou import meters as _meters
-from ...contrastyou.losses.kl import KL_div, class2one_hot
 from ...contrastyou.meters import AverageValueMeter
 from .finetune import unzip_twice_transformed_labeled
+from .helper import supervised_loss
 from .semi import SemiSupervisedEpocher
 
 TRUE_LABEL, FAKE_LABEL = 1, 0
@@ -125,15 +125,7 @@ class AdversarialEpocher(SemiSupervisedEpocher):
         # ---- update segmentation (:148-173)
         labeled_logits = self._model(labeled_image)
         target = labeled_target.squeeze(1)
-        fused = (isinstance(self._sup_criterion, KL_div) and labeled_logits.is_cuda
-                 and labeled_logits.shape[1] == self.num_classes <= 16 and labeled_logits.shape[0] <= 1024)
-        if fused:
-            sup_loss, counts = F_hip.sup_loss_kl_onehot(labeled_logits, target, self._sup_criterion._eps)
-        else:
-            onehot_target = class2one_hot(target, self.num_classes)
-            sup_loss = self._sup_criterion(F_hip.softmax_classes(labeled_logits), onehot_target, disable_assert=True)
-            with torch.no_grad():
-                counts = F_hip.dice_counts(F_hip.argmax_classes(labeled_logits.detach()), target, self.num_classes)
+        sup_loss, counts = supervised_loss(self._sup_criterion, labeled_logits, target, self.num_classes)
         if self._zero is None or self._zero.device != sup_loss.device:
             self._zero = torch.zeros((), dtype=torch.float32, device=sup_loss.device)
         generator_err = disc_loss = self._zero

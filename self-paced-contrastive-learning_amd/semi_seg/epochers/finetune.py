@@ -13,9 +13,10 @@ from ... import ddp as _ddp
 from ... import functional as F_hip
 from ... import native as _n
 from ... import stepgraph as _sg
-from ...contrastyou.losses.kl import KL_div, class2one_hot
+from ...contrastyou.losses.kl import KL_div, class2one_hot  # noqa: F401  (KL_div: the name the reference's module has)
 from ...contrastyou import meters as _meters
 from ...contrastyou.meters import AverageValueMeter, MeterInterface, SurfaceMeter, UniversalDice, VolumeSurfaceMeter
+from .helper import supervised_loss
 
 _FUSED_SUP_LOSS = os.environ.get("SPCL_FUSED_SUP_LOSS", "1") != "0"  # A/B switch: 0 = the seven separate launches
 
@@ -150,6 +151,8 @@ class EvalEpocher(_EpocherBase):
         graph's pool), second sight captured, from then on copy-in + replay + copy-out"""
         key = (tuple(eval_img.shape), eval_img.dtype, tuple(eval_target.shape), eval_target.dtype,
                type(self._sup_criterion).__name__, getattr(self._sup_criterion, "_eps", None), self.num_classes)
+        if hasattr(self._sup_criterion, "graph_key"):
+            key += (self._sup_criterion.graph_key(),)
         e = graphs.entries.get(key)
         if e is None:
             graphs.entries[key] = {"graph": None}
@@ -449,21 +452,20 @@ class FineTuneEpocher(_EpocherBase):
                                          or self._static[1].shape != target.shape
                                          or self._static[1].dtype != target.dtype):
             return None  # ragged last batch: eager
-        return (tuple(image.shape), image.dtype, tuple(target.shape), target.dtype, _ddp.is_distributed(),
-                type(self._sup_criterion).__name__)
+        key = (tuple(image.shape), image.dtype, tuple(target.shape), target.dtype, _ddp.is_distributed(),
+               type(self._sup_criterion).__name__)
+        if hasattr(self._sup_criterion, "graph_key"):  # (its scalars and class weights are baked into a capture)
+            key += (self._sup_criterion.graph_key(),)
+        return key
 
     # the three phases of a step (compute / collective / update), as in the pre-train epocher
     def step_compute(self, labeled_image, labeled_target):
         label_logits = self._forward_pass(labeled_image)
-        fused = (_FUSED_SUP_LOSS and isinstance(self._sup_criterion, KL_div) and label_logits.is_cuda
-                 and label_logits.shape[1] == self.num_classes <= 16 and label_logits.shape[0] <= 1024)
-        if fused:
-            # new_epocher.py:268-282 in one launch: softmax, one-hot, KL_div, arg-max and the Dice counts (and, for the unit
-            # gradient the loop backpropagates, the gradient w.r.t. the logits): functional._SupLossFn
-            sup_loss, counts = F_hip.sup_loss_kl_onehot(label_logits, labeled_target.squeeze(1), self._sup_criterion._eps)
-        else:
-            onehot_target = class2one_hot(labeled_target.squeeze(1), self.num_classes)
-            sup_loss = self._sup_criterion(F_hip.softmax_classes(label_logits), onehot_target, disable_assert=True)
+        # new_epocher.py:268-282: softmax, one-hot, criterion, arg-max and the Dice counts of the training batch ([B, C]
+        # intersections / unions) -- for KL_div in one launch that also writes the gradient w.r.t. the logits for the unit
+        # gradient the loop backpropagates (functional._SupLossFn)
+        sup_loss, self._counts = supervised_loss(self._sup_criterion, label_logits, labeled_target.squeeze(1),
+                                                 self.num_classes, fused=_FUSED_SUP_LOSS)
         if self._unit is None or self._unit.device != sup_loss.device or self._unit.dtype != sup_loss.dtype:
             self._unit = F_hip.register_unit_gradient(torch.ones((), dtype=sup_loss.dtype, device=sup_loss.device))
         if self._flat_params is not None:
@@ -473,12 +475,6 @@ class FineTuneEpocher(_EpocherBase):
         else:
             self._optimizer.zero_grad(set_to_none=True)
             sup_loss.backward(gradient=self._unit)
-        if fused:
-            self._counts = counts
-        else:
-            with torch.no_grad():  # Dice counts of the training batch (new_epocher.py:279-282): [B, C] intersections / unions
-                self._counts = F_hip.dice_counts(F_hip.argmax_classes(label_logits.detach()), labeled_target.squeeze(1),
-                                                 self.num_classes)
         return sup_loss
 
     def step_exchange(self):

@@ -6,6 +6,27 @@ from typing import List
 
 import torch
 
+from ... import functional as F_hip
+from ...contrastyou.losses.kl import KL_div, class2one_hot
+
+
+def supervised_loss(criterion, logits: torch.Tensor, target: torch.Tensor, num_classes: int, fused: bool = True):
+    """the supervised criterion of a training step and the batch's Dice counts (new_epocher.py:268-282) -> (loss, (inter,
+    union)), ``target`` the [B,H,W] label map.  ``KL_div`` takes the fused launch (``functional.sup_loss_kl_onehot``; with
+    ``fused=False`` the composed path), a criterion with ``from_logits`` (contrastyou/losses/dice.py) its own fused kernels,
+    anything else the composed path: softmax, one-hot, criterion, arg-max and Dice counts as separate launches."""
+    on_head = logits.is_cuda and logits.shape[1] == num_classes <= 16 and logits.shape[0] <= 1024
+    if fused and on_head and isinstance(criterion, KL_div):
+        return F_hip.sup_loss_kl_onehot(logits, target, criterion._eps)
+    if on_head and hasattr(criterion, "from_logits"):
+        loss = criterion.from_logits(logits, target)
+        return loss, criterion.last_counts
+    onehot_target = class2one_hot(target, num_classes)
+    loss = criterion(F_hip.softmax_classes(logits), onehot_target, disable_assert=True)
+    with torch.no_grad():
+        counts = F_hip.dice_counts(F_hip.argmax_classes(logits.detach()), target, num_classes)
+    return loss, counts
+
 
 def _label_encode(items):
     index = {v: i for i, v in enumerate(sorted(set(items)))}

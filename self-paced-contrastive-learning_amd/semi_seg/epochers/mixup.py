@@ -9,7 +9,7 @@ import random
 import torch
 
 from ... import functional as F_hip
-from ...contrastyou.losses.kl import KL_div, class2one_hot
+from .helper import supervised_loss
 from .semi import SemiSupervisedEpocher
 
 
@@ -52,15 +52,7 @@ class MixUpEpocher(SemiSupervisedEpocher):
             unzip_twice_transformed_pair(labeled_data, self._device)
         label_logits = self.forward_pass(labeled_image=labeled_image, labeled_image_tf=labeled_image_tf)
         target = labeled_target.squeeze(1)
-        fused = (isinstance(self._sup_criterion, KL_div) and label_logits.is_cuda
-                 and label_logits.shape[1] == self.num_classes <= 16 and label_logits.shape[0] <= 1024)
-        if fused:
-            sup_loss, counts = F_hip.sup_loss_kl_onehot(label_logits, target, self._sup_criterion._eps)
-        else:
-            onehot_target = class2one_hot(target, self.num_classes)
-            sup_loss = self._sup_criterion(F_hip.softmax_classes(label_logits), onehot_target, disable_assert=True)
-            with torch.no_grad():
-                counts = F_hip.dice_counts(F_hip.argmax_classes(label_logits.detach()), target, self.num_classes)
+        sup_loss, counts = supervised_loss(self._sup_criterion, label_logits, target, self.num_classes)
         reg_loss = self.regularization(labeled_image=labeled_image, labeled_image_tf=labeled_image_tf,
                                        labeled_target=labeled_target, labeled_target_tf=labeled_target_tf, seed=seed)
         total_loss = sup_loss + reg_loss

@@ -18,10 +18,9 @@ from torch import nn
 from ... import ddp as _ddp
 from ... import functional as F_hip
 from ...contrastyou import meters as _meters
-from ...contrastyou.losses.kl import KL_div, class2one_hot
 from ...contrastyou.meters import AverageValueMeter, UniversalDice
 from .finetune import _EpocherBase, unzip_twice_transformed_labeled
-from .helper import FixRandomSeed, TensorRandomFlip
+from .helper import FixRandomSeed, TensorRandomFlip, supervised_loss
 
 
 class SemiSupervisedEpocher(_EpocherBase):
@@ -141,15 +140,7 @@ class SemiSupervisedEpocher(_EpocherBase):
             labeled_image=labeled_image, unlabeled_image=unlabeled_image, unlabeled_image_tf=unlabeled_image_tf)
         unlabeled_logits_tf = F_hip.flip_batch(unlabeled_logits, flags)
         target = labeled_target.squeeze(1)
-        fused = (isinstance(self._sup_criterion, KL_div) and label_logits.is_cuda
-                 and label_logits.shape[1] == self.num_classes <= 16 and label_logits.shape[0] <= 1024)
-        if fused:
-            sup_loss, counts = F_hip.sup_loss_kl_onehot(label_logits, target, self._sup_criterion._eps)
-        else:
-            onehot_target = class2one_hot(target, self.num_classes)
-            sup_loss = self._sup_criterion(F_hip.softmax_classes(label_logits), onehot_target, disable_assert=True)
-            with torch.no_grad():
-                counts = F_hip.dice_counts(F_hip.argmax_classes(label_logits.detach()), target, self.num_classes)
+        sup_loss, counts = supervised_loss(self._sup_criterion, label_logits, target, self.num_classes)
         reg_loss = self.regularization(
             unlabeled_tf_logits=unlabeled_tf_logits, unlabeled_logits_tf=unlabeled_logits_tf, seed=seed,
             unlabeled_image=unlabeled_image, unlabeled_image_tf=unlabeled_image_tf, label_group=unl_group,

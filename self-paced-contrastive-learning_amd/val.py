@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from .contrastyou import success
-from .contrastyou.losses.kl import KL_div
+from .contrastyou.losses.dice import build_sup_criterion
 from .semi_seg.data.creator import get_data
 from .semi_seg.trainers.finetune import FineTuneTrainer
 
@@ -96,7 +96,8 @@ def _val(*, model: nn.Module, labeled_data_ratio: float, data_params: Dict[str, 
     loaders = dict(zip(names, get_data(data_params=data_cfg, labeled_loader_params=labeled_loader_params,
                                        unlabeled_loader_params=unlabeled_loader_params, pretrain=False)))
     trainer_cfg["save_dir"] = _ratio_dir(main_save_dir, loaders["labeled_loader"])
-    trainer = FineTuneTrainer(model=model, criterion=KL_div(verbose=False), config=config, **loaders, **trainer_cfg)
+    # (the reference's KL_div(verbose=False) unless the config has a SupCriterion section)
+    trainer = FineTuneTrainer(model=model, criterion=build_sup_criterion(config), config=config, **loaders, **trainer_cfg)
     trainer.init()
     trainer.start_training()
     success(save_dir=trainer.save_dir)
