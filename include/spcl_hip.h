@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 31
+#define SPCL_ABI_VERSION 32
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -1396,6 +1396,37 @@ int spcl_sup_dice_forward(const float* logits, const int64_t* labels, const floa
 int spcl_sup_dice_backward(const float* logits, const int64_t* labels, const float* class_weight, const float* coef, int N,
                            int C, int H, int W, float dice_weight, float kl_weight, int per_sample, float eps,
                            const float* gscale, float* dlogits, void* stream);
+
+/* ---------------------------------------------------------------- boundary loss (csrc/boundary.hip) -----------------
+ * Signed Euclidean distance maps of a label batch and the boundary criterion of contrastyou/losses/boundary.py (Kervadec et
+ * al., MIDL 2019; not in the reference; ABI 32).  For sample n and listed class c, m = (labels[n] == c); a label outside the
+ * class list's values belongs to no listed class.  d2(x) = the smallest integer (dy)^2 + (dx)^2 from pixel x to a pixel of
+ * the same slice whose membership in m differs from x's (unit spacing);
+ *   phi[n, c, x] = +sqrt(d2) outside m,  -(sqrt(d2) - 1) inside m  (float64 square root, rounded once to f32),
+ *   phi == 0 on the whole slice where no pixel of the opposite membership exists (class absent, or class fills the slice).
+ *   L_B = 1 / (N S H W) sum_{n, s, x} softmax(logits)[n, classes[s], x] * phi[n, s, x]
+ *
+ *   spcl_signed_distance_maps: labels [N][H][W] int64, classes = HOST array of n_classes <= 16 distinct values >= 0,
+ *                    phi [N][H][W][n_classes] f32 (channels-last, beside the logits).  H, W <= 1024, N <= 1024.  Two launches
+ *                    (column scans into two uint16 planes per (n, class): vertical distance to the nearest pixel inside /
+ *                    outside m, 0xFFFF = none; row minima over integer squares in LDS, one wave per row), no atomics, nothing
+ *                    read back: the same input gives the same bits.  ws: spcl_signed_distance_workspace_bytes(N, H, W,
+ *                    n_classes) bytes (0 = unsupported shape), 16-byte aligned.
+ *   spcl_boundary_forward: logits [N][H][W][C] f32 (C <= 16, N <= 1024), classes = HOST array of n_classes distinct values in
+ *                    [0, C), alpha = a DEVICE f32 scalar.  lb[0] = L_B, loss[0] = alpha * L_B.  Two launches: float64 partials
+ *                    per workgroup, then their sum in index order (no ticket, no fence, no floating-point atomics, no memset):
+ *                    bitwise reproducible.  ws: spcl_boundary_workspace_bytes(N, H, W) bytes, 8-byte aligned.
+ *   spcl_boundary_backward: one launch: dlogits [N][H][W][C] = g p_k (a_k - sum_c a_c p_c), a_c = alpha phi_c / (N S H W) for a
+ *                    listed class and 0 otherwise, g = gscale[0] (a device scalar) or 1 when gscale is NULL.  alpha is read
+ *                    on the device: a captured call replays with whatever the scalar holds then. */
+size_t spcl_signed_distance_workspace_bytes(int N, int H, int W, int n_classes);
+int spcl_signed_distance_maps(const int64_t* labels, int N, int H, int W, const int* classes, int n_classes, float* phi,
+                              void* ws, size_t ws_bytes, void* stream);
+size_t spcl_boundary_workspace_bytes(int N, int H, int W);
+int spcl_boundary_forward(const float* logits, const float* phi, const int* classes, int n_classes, int N, int C, int H, int W,
+                          const float* alpha, float* loss, float* lb, void* ws, size_t ws_bytes, void* stream);
+int spcl_boundary_backward(const float* logits, const float* phi, const int* classes, int n_classes, int N, int C, int H, int W,
+                           const float* alpha, const float* gscale, float* dlogits, void* stream);
 
 #ifdef __cplusplus
 }

@@ -106,24 +106,30 @@ class WeightedKL(DiceKLLoss):
         super().__init__(dice_weight=0.0, kl_weight=1.0, class_weight=class_weight, eps=eps)
 
 
-SUP_CRITERIA = ("kl", "dice", "dice_kl", "weighted_kl")
+SUP_CRITERIA = ("kl", "dice", "dice_kl", "weighted_kl", "boundary")
+_DICE_KL_KEYS = ("dice_weight", "kl_weight", "class_weight", "include_background", "per_sample", "smooth")
+_BOUNDARY_KEYS = ("alpha", "alpha_step", "alpha_max", "classes")
 
 
 def build_sup_criterion(config=None):
     """the supervised criterion of a run from the optional config section ``SupCriterion: {name: kl | dice | dice_kl |
-    weighted_kl, dice_weight, kl_weight, class_weight, include_background, per_sample, smooth}``; without the section:
-    ``KL_div(verbose=False)``, the reference's"""
+    weighted_kl | boundary, dice_weight, kl_weight, class_weight, include_background, per_sample, smooth}``; ``boundary``
+    (contrastyou/losses/boundary.py) also takes ``alpha, alpha_step, alpha_max, classes`` and hands ``dice_kl``'s keys to its
+    region term; without the section: ``KL_div(verbose=False)``, the reference's"""
     from .kl import KL_div
     section = dict((config or {}).get("SupCriterion") or {})
     name = section.pop("name", "kl")
     if name not in SUP_CRITERIA:
         raise ValueError(f"SupCriterion.name must be one of {SUP_CRITERIA}, given {name!r}")
     allowed = {"kl": (), "dice": ("class_weight", "include_background", "per_sample", "smooth"),
-               "dice_kl": ("dice_weight", "kl_weight", "class_weight", "include_background", "per_sample", "smooth"),
-               "weighted_kl": ("class_weight",)}[name]
+               "dice_kl": _DICE_KL_KEYS, "weighted_kl": ("class_weight",), "boundary": _BOUNDARY_KEYS + _DICE_KL_KEYS}[name]
     unknown = sorted(set(section) - set(allowed))
     if unknown:
         raise ValueError(f"SupCriterion {name!r} does not take {unknown} (it takes {list(allowed)})")
     if name == "kl":
         return KL_div(verbose=False)
+    if name == "boundary":
+        from .boundary import BoundaryLoss
+        own = {k: section.pop(k) for k in _BOUNDARY_KEYS if k in section}
+        return BoundaryLoss(region=DiceKLLoss(**section), **own)
     return {"dice": SoftDiceLoss, "dice_kl": DiceKLLoss, "weighted_kl": WeightedKL}[name](**section)

@@ -2747,6 +2747,97 @@ def sup_dice_kl_onehot(logits, labels, weight, *, dice_weight=1.0, kl_weight=1.0
     return loss, counts, parts
 
 
+_SDM_WS, _BOUNDARY_WS = {}, {}  # (device, stream, shape) -> workspace, as _SUP_DICE_WS
+
+
+def _class_list(classes, what):
+    cl = tuple(int(c) for c in classes)
+    if not cl or len(cl) > 16 or len(set(cl)) != len(cl) or min(cl) < 0:
+        raise ValueError(f"{what}: 1 to 16 distinct non-negative classes, given {cl}")
+    return cl
+
+
+def signed_distance_maps(labels: torch.Tensor, classes) -> torch.Tensor:
+    """[N,H,W] integer labels -> logical [N, |classes|, H, W] f32 (channels-last storage) signed Euclidean distance maps
+    (csrc/boundary.hip, INTEGRATION.md "Boundary loss"): +sqrt(d2) outside ``labels == c``, -(sqrt(d2) - 1) inside, 0 on a
+    slice where the class is absent or fills it; unit pixel spacing.  Two launches, nothing read back, no gradient."""
+    cl = _class_list(classes, "signed_distance_maps")
+    _n.require_gpu(labels)
+    if labels.dim() != 3:
+        raise ValueError(f"labels [N,H,W], given {tuple(labels.shape)}")
+    lab = labels.detach().long().contiguous()
+    N, H, W = lab.shape
+    if N > 1024 or H > 1024 or W > 1024 or min(N, H, W) < 1:
+        raise ValueError(f"signed_distance_maps: 1 <= N, H, W <= 1024, given {(N, H, W)}")
+    S, dev = len(cl), lab.device
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream, N, H, W, S)
+    ws = _SDM_WS.get(key)
+    if ws is None:
+        ws = _SDM_WS[key] = torch.empty(_n.call("spcl_signed_distance_workspace_bytes", N, H, W, S), dtype=torch.uint8,
+                                        device=dev)
+    phi = torch.empty(N, H, W, S, dtype=torch.float32, device=dev)
+    _n.call("spcl_signed_distance_maps", _n.ptr(lab), N, H, W, (ctypes.c_int * S)(*cl), S, _n.ptr(phi), _n.ptr(ws),
+            ws.numel(), _n.stream())
+    return phi.permute(0, 3, 1, 2)
+
+
+class _BoundaryFn(torch.autograd.Function):
+    """``alpha * L_B``, L_B = mean over (n, listed class, pixel) of softmax(logits) * phi (csrc/boundary.hip); ``alpha`` is a
+    device scalar read by the kernels, so a captured call replays with what it holds then.  ``out`` receives L_B itself."""
+
+    @staticmethod
+    def forward(ctx, logits, phi, classes, alpha, out):
+        _n.require_gpu(logits, phi, alpha)
+        ls = _class_map_storage(logits.detach())
+        ps = _class_map_storage(phi.detach())
+        N, H, W, C = ls.shape
+        S = len(classes)
+        if tuple(ps.shape) != (N, H, W, S):
+            raise AssertionError(f"distance maps {tuple(ps.shape)} do not match {(N, H, W, S)}")
+        if alpha.dtype != torch.float32 or alpha.numel() != 1:
+            raise AssertionError("alpha must be a float32 device scalar")
+        dev = ls.device
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream, N, H, W)
+        ws = _BOUNDARY_WS.get(key)
+        if ws is None:
+            ws = _BOUNDARY_WS[key] = torch.empty(max(_n.call("spcl_boundary_workspace_bytes", N, H, W), 8),
+                                                 dtype=torch.uint8, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)  # alpha * L_B
+        mean = torch.empty((), dtype=torch.float32, device=dev)  # L_B
+        cl = (ctypes.c_int * S)(*classes)
+        _n.call("spcl_boundary_forward", _n.ptr(ls), _n.ptr(ps), cl, S, N, C, H, W, _n.ptr(alpha), _n.ptr(loss),
+                _n.ptr(mean), _n.ptr(ws), ws.numel(), _n.stream())
+        out.append(mean)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(ls, ps, alpha)
+            ctx.classes = classes
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        ls, ps, alpha = ctx.saved_tensors
+        N, H, W, C = ls.shape
+        S = len(ctx.classes)
+        gs = None if is_unit_gradient(g) else g.detach().reshape(1).float().contiguous()
+        dl = torch.empty_like(ls)
+        _n.call("spcl_boundary_backward", _n.ptr(ls), _n.ptr(ps), (ctypes.c_int * S)(*ctx.classes), S, N, C, H, W,
+                _n.ptr(alpha), _n.ptr(gs), _n.ptr(dl), _n.stream())
+        return dl.permute(0, 3, 1, 2), None, None, None, None
+
+
+def boundary_loss(logits, phi, classes, alpha, *, with_mean=False):
+    """``alpha * L_B`` of [N,C,H,W] logits against the signed distance maps ``phi`` [N,|classes|,H,W] of ``classes`` (distinct,
+    in [0, C)); ``alpha`` a float32 device scalar (``_BoundaryFn``).  ``with_mean=True`` -> (loss, L_B), L_B a device scalar
+    without a gradient."""
+    cl = _class_list(classes, "boundary_loss")
+    _n.require_gpu(logits, phi, alpha)
+    if logits.dim() != 4 or max(cl) >= logits.shape[1]:
+        raise ValueError(f"boundary_loss: logits [N,C,H,W] and classes in [0, C), given {tuple(logits.shape)} and {cl}")
+    out = []
+    loss = _BoundaryFn.apply(logits, phi, cl, alpha, out)
+    return (loss, out[0]) if with_mean else loss
+
+
 def one_hot_classes(labels: torch.Tensor, K: int) -> torch.Tensor:
     """class2one_hot: [N,H,W] integer labels -> logical [N,K,H,W] f32 one-hot (NHWC storage)."""
     _n.require_gpu(labels)

@@ -16,7 +16,7 @@ from ... import stepgraph as _sg
 from ...contrastyou.losses.kl import KL_div, class2one_hot  # noqa: F401  (KL_div: the name the reference's module has)
 from ...contrastyou import meters as _meters
 from ...contrastyou.meters import AverageValueMeter, MeterInterface, SurfaceMeter, UniversalDice, VolumeSurfaceMeter
-from .helper import supervised_loss
+from .helper import begin_epoch, supervised_loss
 
 _FUSED_SUP_LOSS = os.environ.get("SPCL_FUSED_SUP_LOSS", "1") != "0"  # A/B switch: 0 = the seven separate launches
 
@@ -366,6 +366,7 @@ class FineTuneEpocher(_EpocherBase):
         self._optimizer = optimizer
         self._labeled_loader = labeled_loader
         self._sup_criterion = sup_criterion
+        begin_epoch(sup_criterion, cur_epoch)
         self._flat_params = flat_params
         from ...optim import is_fused
         if flat_params is not None:

@@ -28,6 +28,13 @@ def supervised_loss(criterion, logits: torch.Tensor, target: torch.Tensor, num_c
     return loss, counts
 
 
+def begin_epoch(criterion, cur_epoch: int):
+    """tell a criterion with an epoch schedule (``BoundaryLoss``: its alpha) which epoch a training epocher runs.  Only the
+    criterion's CLASS is asked for ``set_epoch``: for any other criterion nothing of the instance is looked up or changed."""
+    if hasattr(type(criterion), "set_epoch"):
+        criterion.set_epoch(cur_epoch)
+
+
 def _label_encode(items):
     index = {v: i for i, v in enumerate(sorted(set(items)))}
     return [index[v] for v in items]

@@ -20,7 +20,7 @@ from ... import functional as F_hip
 from ...contrastyou import meters as _meters
 from ...contrastyou.meters import AverageValueMeter, UniversalDice
 from .finetune import _EpocherBase, unzip_twice_transformed_labeled
-from .helper import FixRandomSeed, TensorRandomFlip, supervised_loss
+from .helper import FixRandomSeed, TensorRandomFlip, begin_epoch, supervised_loss
 
 
 class SemiSupervisedEpocher(_EpocherBase):
@@ -32,6 +32,7 @@ class SemiSupervisedEpocher(_EpocherBase):
         self._optimizer = optimizer
         self._labeled_loader, self._unlabeled_loader = labeled_loader, unlabeled_loader
         self._sup_criterion = sup_criterion
+        begin_epoch(sup_criterion, cur_epoch)
         self._affine_transformer = TensorRandomFlip(axis=[1, 2], threshold=0.8)
         self._two_stage, self._disable_bn = two_stage, disable_bn
         self._flat_params = flat_params
