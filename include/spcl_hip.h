@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 32
+#define SPCL_ABI_VERSION 33
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -1427,6 +1427,39 @@ int spcl_boundary_forward(const float* logits, const float* phi, const int* clas
                           const float* alpha, float* loss, float* lb, void* ws, size_t ws_bytes, void* stream);
 int spcl_boundary_backward(const float* logits, const float* phi, const int* classes, int n_classes, int N, int C, int H, int W,
                            const float* alpha, const float* gscale, float* dlogits, void* stream);
+
+/* ---------------------------------------------------------------- pseudo-labelling baseline (csrc/pseudo_label.hip) -----------
+ * Self-training with confidence-thresholded pseudo-labels (FixMatch) and the self-adaptive per-class thresholds of FreeMatch
+ * (Wang et al., ICLR 2023); not in the reference.  One launch.
+ *
+ *   spcl_pseudo_label_ce: teacher and student_logits are [N][H][W][C] f32 class maps, 1 <= C <= 16; the teacher map is read
+ *                    through the per-sample flip flags (bit 0 flips H, bit 1 flips W, NULL: no flips).  Per pixel of the
+ *                    student's frame: q = softmax(flip(teacher)); y = argmax_c of the teacher's LOGITS (exact; a tie goes to
+ *                    the lowest class); conf = max_c q_c, formed in f32 as 1 / z with z the sum of exp(logit - max logit);
+ *                    keep = conf >= tau[y] (a NaN confidence keeps nothing); p = softmax(student_logits); term = keep ?
+ *                    -log p_y : 0.  loss = weight / M * sum term with M = N H W (FixMatch's mean over ALL pixels, not over
+ *                    the kept ones); dstudent_k = keep ? weight / M * (p_k - [k == y]) : 0 for a unit upstream gradient
+ *                    (exact zeros at dropped pixels; the teacher gets no gradient).
+ *                    stats[0] = sum conf, stats[1 + c] = sum q_c over ALL pixels, in double.  hist[c] = the number of pixels
+ *                    with y == c, hist[C + c] = the number of KEPT pixels with y == c (exact integers).  label (nullable,
+ *                    [N][H][W] bytes) receives keep ? y : 255.
+ *                    tau: C device floats.  state == NULL (fixed thresholds): tau is read only.  state != NULL (self-adaptive):
+ *                    state = (tau_g, ptilde[0 .. C)) in double on the device; the pixels of THIS launch compare against tau as
+ *                    it stands on entry, and once the sums are complete the closing workgroup stores in place, in double,
+ *                      tau_g' = m tau_g + (1 - m) stats[0] / M,   ptilde'[c] = m ptilde[c] + (1 - m) stats[1 + c] / M,
+ *                      tau'[c] = (float)(ptilde'[c] / max_c ptilde' * tau_g')
+ *                    with m = momentum in [0, 1): a one-step lag against FreeMatch's Algorithm 1, which counts the current
+ *                    batch into the threshold it is compared with.  Nothing is read back by the host.
+ *                    Every sum is a fixed association (per thread in pixel order, wave butterfly, waves in order, workgroup
+ *                    rows in index order by the last workgroup to take a ticket): all outputs are bitwise reproducible.  No
+ *                    floating-point atomics; one 4-byte memset (the ticket).  Shapes refused: N, H or W <= 0, C outside
+ *                    [1, 16], N H W >= 2^31.  ws: spcl_pseudo_label_workspace_bytes(N, C, H, W) bytes (0 for a refused
+ *                    shape), 8-byte aligned. */
+size_t spcl_pseudo_label_workspace_bytes(int N, int C, int H, int W);
+int spcl_pseudo_label_ce(const float* teacher, const float* student_logits, int N, int C, int H, int W,
+                         const uint8_t* flags_teacher, float* tau, double* state, double momentum, float weight, float* loss,
+                         float* dstudent, double* stats, unsigned long long* hist, uint8_t* label, void* ws, size_t ws_bytes,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -3771,6 +3771,65 @@ def ucmt_softmax_mse(teacher, noisy_list, student_logits, threshold, weight=1.0,
     return _PixelCriterionFn.apply(student_logits, launch)
 
 
+# ------------------------------------------------------------------------------- pseudo-labelling (csrc/pseudo_label.hip)
+def pseudo_label_state(C, device):
+    """``(tau, state)`` of the self-adaptive thresholds at their initial values (FreeMatch, Algorithm 1): ``tau`` f32 [C] and
+    ``state = (tau_g, ptilde[0 .. C))`` f64 [1 + C], every entry ``1 / C``"""
+    C = int(C)
+    if not 1 <= C <= 16:
+        raise ValueError(f"pseudo_label_state: C = {C} (1 <= C <= 16)")
+    return (torch.full((C,), 1.0 / C, dtype=torch.float32, device=device),
+            torch.full((1 + C,), 1.0 / C, dtype=torch.float64, device=device))
+
+
+def _pseudo_label_vector(t, name, dtype, n, dev):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"pseudo_label_ce: `{name}` must be a {dtype} [{n}] tensor on {dev}, got {type(t).__name__}")
+    _n.require_gpu(t)
+    if t.dtype != dtype or t.dim() != 1 or t.numel() != n or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"pseudo_label_ce: `{name}` must be a contiguous {dtype} [{n}] tensor on {dev}: got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+    return t.detach()
+
+
+def pseudo_label_ce(teacher, student_logits, tau, weight=1.0, flags=None, state=None, momentum=0.999, out=None):
+    """FixMatch's masked cross-entropy of logical [N, C, H, W] maps in one launch: ``weight * mean over ALL pixels of [conf >=
+    tau[y]] * cross_entropy(student_logits, y)`` with ``y = argmax(flip(teacher))`` (the lowest class on a tie) and ``conf =
+    max softmax(flip(teacher))``.  The gradient goes to the student only.  ``tau``: f32 [C] on the device.  ``state`` (f64
+    [1 + C] on the device, see ``pseudo_label_state``) switches FreeMatch's self-adaptive thresholds on: this call compares
+    against ``tau`` as it stands, then the same launch moves ``state`` and ``tau`` in place by the batch's statistics with
+    ``momentum`` -- nothing is read back.  ``out`` (a list) receives ``(stats, hist, label)``: ``stats`` f64 [1 + C] = (sum
+    conf, sum softmax(teacher)_c) over all pixels, ``hist`` int64 [2 C] = (pixels per class, kept pixels per class), ``label``
+    uint8 [N, H, W] = the pseudo-label of a kept pixel and 255 elsewhere, in the student's frame."""
+    weight, momentum = float(weight), float(momentum)
+    if not 0.0 <= momentum < 1.0:
+        raise ValueError(f"pseudo_label_ce: momentum {momentum} outside [0, 1)")
+
+    def launch():
+        _n.require_gpu(teacher, student_logits)
+        ts, ss = _class_map_storage(teacher.detach()), _class_map_storage(student_logits.detach())
+        if ts.shape != ss.shape or ts.device != ss.device:
+            raise AssertionError(f"class maps {tuple(ts.shape)} on {ts.device} / {tuple(ss.shape)} on {ss.device} differ")
+        N, H, W, C = ss.shape
+        dev = ss.device
+        tv = _pseudo_label_vector(tau, "tau", torch.float32, C, dev)
+        sv = None if state is None else _pseudo_label_vector(state, "state", torch.float64, 1 + C, dev)
+        fl = _flip_flags_arg(flags, N, dev)
+        loss, ds = torch.empty((), dtype=torch.float32, device=dev), torch.empty_like(ss)
+        ws = torch.empty(max(8, _n.call("spcl_pseudo_label_workspace_bytes", N, C, H, W)), dtype=torch.uint8, device=dev)
+        stats = torch.empty(1 + C, dtype=torch.float64, device=dev)
+        hist = torch.empty(2 * C, dtype=torch.int64, device=dev)
+        label = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if out is not None else None
+        _n.call("spcl_pseudo_label_ce", _n.ptr(ts), _n.ptr(ss), N, C, H, W, _n.ptr(fl), _n.ptr(tv), _n.ptr(sv),
+                c_double(momentum), c_float(weight), _n.ptr(loss), _n.ptr(ds), _n.ptr(stats), _n.ptr(hist), _n.ptr(label),
+                _n.ptr(ws), ws.numel(), _n.stream())
+        if out is not None:
+            out.extend((stats, hist, label))
+        return loss, ds
+
+    return _PixelCriterionFn.apply(student_logits, launch)
+
+
 # ------------------------------------------------------------------------------------------------ mix-up (csrc/semi_reg.hip)
 class MixupPlan:
     """One mix-up draw (mixup.py:19-32) for a batch of B labelled samples and their second views: ``lam`` (the host's float64),

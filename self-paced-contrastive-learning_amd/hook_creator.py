@@ -28,7 +28,10 @@ this one follows ``DiscreteMIConsistencyParams`` key for key.  Refused during pr
 ``IICRegParameters`` builds the IIC-estimator baseline (``create_iic_estimator_hooks``: an ``IICEstimatorArray`` over the
 encoder and decoder features, one hook per estimator): the keys of config/specific/iic.yaml (``EncoderParams``,
 ``DecoderParams``, ``LossParams``, ``weight``, ``enforce_matching``) plus ``feature_names`` and ``feature_importance``, which
-the reference's old-API ``IICTrainer`` (trainer.py:64-95) reads from ``FeatureExtractor``.  Refused during pre-training."""
+the reference's old-API ``IICTrainer`` (trainer.py:64-95) reads from ``FeatureExtractor``.  Refused during pre-training.
+``PseudoLabelParameters`` builds the pseudo-labelling baseline (``create_pseudo_label_hook``: FixMatch's confidence-thresholded
+self-training, optionally with FreeMatch's self-adaptive thresholds): ``weight``, ``threshold``, ``adaptive``, ``momentum``,
+``teacher`` and, for ``teacher: ema``, ``alpha`` / ``weight_decay``.  Not in the reference.  Refused during pre-training."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -46,6 +49,7 @@ _SEMI_SECTIONS = (
     ("MineParameters", "create_mine_hooks", True, False),
     ("PICAConsistencyParams", "create_pica_consistency_hook", True, False),
     ("IICRegParameters", "create_iic_estimator_hooks", True, False),
+    ("PseudoLabelParameters", "create_pseudo_label_hook", True, False),
 )
 
 

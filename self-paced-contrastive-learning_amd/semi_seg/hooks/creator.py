@@ -9,7 +9,8 @@ trainer-registry keys (semi_seg/trainers/__init__.py:11-12).  ``create_uc_mean_t
 (trainer.py:39-60, registry key ``midl``) and ``create_mine_hooks`` for ``MineTrainer`` (trainer.py:98-107, registry key
 ``mine``).  ``create_pica_hooks`` / ``create_pica_consistency_hook`` are the two discrete-MI factories with the PICA criteria
 (contrastyou/losses/pica_loss.py; the reference pairs them with the cluster heads in ``PICALossWrapper``,
-semi_seg/utils.py:242-263, and has no factory of its own for them)."""
+semi_seg/utils.py:242-263, and has no factory of its own for them).  ``create_pseudo_label_hook`` builds the pseudo-labelling
+baseline (FixMatch / FreeMatch thresholds), which the reference lacks altogether."""
 from typing import List, Union
 
 from ...contrastyou.hooks.base import CombineTrainerHook
@@ -23,6 +24,7 @@ from .midl import MIDLPaperTrainerHook
 from .mine import MineTrainHook
 from .mt import MeanTeacherTrainerHook
 from .pica import PICATrainHook
+from .pseudolabel import PseudoLabelTrainerHook
 from .ucmt import UCMeanTeacherTrainerHook
 
 
@@ -154,6 +156,14 @@ def create_uc_mean_teacher_hook(*, model, weight: float, max_epoch: int, alpha: 
         raise NotImplementedError(f"uncertainty-aware mean teacher criterion {name!r}: only 'mse' is mirrored")
     return UCMeanTeacherTrainerHook(name="ucmeanteacher", weight=weight, model=model, max_epoch=max_epoch, alpha=alpha,
                                     weight_decay=weight_decay, **uc)
+
+
+def create_pseudo_label_hook(*, model, weight: float, threshold=0.95, adaptive: bool = False, momentum: float = 0.999,
+                             teacher: str = "self", alpha: float = 0.999, weight_decay: float = 1e-5):
+    """``PseudoLabelParameters``: confidence-thresholded self-training on the unlabelled batch (semi_seg/hooks/pseudolabel.py);
+    ``alpha`` and ``weight_decay`` are the mean teacher's and matter with ``teacher="ema"`` only"""
+    return PseudoLabelTrainerHook(name="pseudolabel", weight=weight, model=model, threshold=threshold, adaptive=adaptive,
+                                  momentum=momentum, teacher=teacher, alpha=alpha, weight_decay=weight_decay)
 
 
 def create_entropy_min_hook(*, weight: float):
