@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 33
+#define SPCL_ABI_VERSION 34
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -1460,6 +1460,58 @@ int spcl_pseudo_label_ce(const float* teacher, const float* student_logits, int 
                          const uint8_t* flags_teacher, float* tau, double* state, double momentum, float weight, float* loss,
                          float* dstudent, double* stats, unsigned long long* hist, uint8_t* label, void* ws, size_t ws_bytes,
                          void* stream);
+
+/* ---------------------------------------------------------------- label-guided pixel contrast (csrc/pixel_contrast.hip) -------
+ * A class-balanced sample of decoder cells chosen on the device, the gather of their feature rows and a supervised-contrastive
+ * criterion over the gathered, projected rows; not in the reference.  Nothing is read back, the launch count of every entry is
+ * fixed, every entry is capturable, all outputs are bitwise reproducible (integer atomics only).
+ *
+ *   spcl_pixel_sample: cell_label is int32 [ncells] (flat index i = b h w + y w + x); a cell is eligible for class c iff
+ *                    cell_label[i] == c with 0 <= c < C (any other value: ineligible).  key(i) = fmix32((((i + 1) *
+ *                    0x9E3779B1) mod 2^32) ^ *seed), fmix32 the MurmurHash3 finaliser (h ^= h >> 16; h *= 0x85EBCA6B;
+ *                    h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16, mod 2^32), seed ONE 32-bit word in device memory (read by
+ *                    the kernels: a captured call replays with what the word holds then).  Keys of distinct cells are
+ *                    distinct.  Per class the min(K, n_c) eligible cells with the smallest keys are chosen: idx int32 [C][K]
+ *                    receives their flat indices in ascending index order, then -1; count int32 [C] = min(K, n_c).
+ *                    A radix select of the K-th key per class (four byte histograms), a count and a write pass in index order:
+ *                    one memset and six launches.  Refused: C outside [2, 16], K outside [1, 1024], C K > 4096, ncells < 1.
+ *                    ws: spcl_pixel_sample_workspace_bytes(ncells) bytes (0 for ncells < 1), 4-byte aligned.
+ *   spcl_rows_gather_forward: rows[m][0 .. Cf) = feat[idx[m]][0 .. Cf) as f32, m < M; feat is the channels-last storage of the
+ *                    feature map, f32 or bf16 (SPCL_F32 / SPCL_BF16), cell i at feat + i * cs elements (cs >= Cf).  A row whose
+ *                    index is negative (or >= ncells) is exactly zero.
+ *   spcl_rows_gather_backward: dfeat (the storage dtype and pitch of feat, ncells * cs elements) is zero everywhere except
+ *                    dfeat[idx[m]][0 .. Cf) = drows[m] (rounded to nearest even for bf16).  The indices >= 0 must be distinct
+ *                    (the sampler's are): one memset and plain stores, no atomics.
+ *   spcl_pixel_supcon_forward: z is [M = C K][d] f32 rows (contiguous, 16-byte aligned).  Slot m = c K + j has class c and is
+ *                    VALID iff j < count[c] (count int32 [C] on the device, clamped to [0, K]); no label vector or mask is
+ *                    read.  For a valid row i: A(i) = the valid rows other than i, P(i) = those of i's class, I = the valid
+ *                    rows with |P(i)| >= 1;
+ *                      l_i = -(1 / |P(i)|) sum_{p in P(i)} [ z_i.z_p / t - log sum_{a in A(i)} exp(z_i.z_a / t) ],
+ *                      loss = (1 / |I|) sum_{i in I} l_i,   0 when I is empty.
+ *                    Invalid rows are never loaded (they may hold NaN).  Products on the exact-f32 MFMA in one contraction
+ *                    order; a row block's column tiles are dealt to up to 8 workgroups (a function of M alone), each keeps row
+ *                    sums with a running maximum in tile order, a closing workgroup joins them in split order and adds the
+ *                    rows' terms in double in index order.  The workspace keeps the rows' log-sums for the backward call.
+ *                    Two launches.
+ *   spcl_pixel_supcon_backward: dz [M][d] = (*gscale, or 1 for NULL) * dloss/dz; exact zeros in invalid rows and everywhere
+ *                    when I is empty.  ws: the workspace the forward call of the SAME z and count left.  Two launches: the
+ *                    similarity tiles are formed again with the same bits (the matrix is never stored) and every column
+ *                    split leaves its share of the gradient in the workspace; the second launch adds them in split order.
+ *                    Refused by both: C outside [2, 16], K outside [1, 1024], C K > 4096, d outside [4, 256] or not a
+ *                    multiple of 4, t <= 0.  ws: spcl_pixel_supcon_workspace_bytes(M, d) bytes (0 for a refused M or d),
+ *                    16-byte aligned. */
+size_t spcl_pixel_sample_workspace_bytes(int ncells);
+int spcl_pixel_sample(const int32_t* cell_label, int ncells, int C, int K, const uint32_t* seed, int32_t* idx, int32_t* count,
+                      void* ws, size_t ws_bytes, void* stream);
+int spcl_rows_gather_forward(const void* feat, int dtype, int ncells, int Cf, int64_t cs, const int32_t* idx, int M, float* rows,
+                             void* stream);
+int spcl_rows_gather_backward(const float* drows, const int32_t* idx, int M, int Cf, void* dfeat, int dtype, int ncells,
+                              int64_t cs, void* stream);
+size_t spcl_pixel_supcon_workspace_bytes(int M, int d);
+int spcl_pixel_supcon_forward(const float* z, const int32_t* count, int C, int K, int d, float t, float* loss, void* ws,
+                              size_t ws_bytes, void* stream);
+int spcl_pixel_supcon_backward(const float* z, const int32_t* count, int C, int K, int d, float t, const float* gscale,
+                               void* ws, size_t ws_bytes, float* dz, void* stream);
 
 #ifdef __cplusplus
 }

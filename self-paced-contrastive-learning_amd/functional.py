@@ -3830,6 +3830,179 @@ def pseudo_label_ce(teacher, student_logits, tau, weight=1.0, flags=None, state=
     return _PixelCriterionFn.apply(student_logits, launch)
 
 
+# --------------------------------------------------------------------- label-guided pixel contrast (csrc/pixel_contrast.hip)
+PIXEL_CONTRAST_MAX_C, PIXEL_CONTRAST_MAX_K, PIXEL_CONTRAST_MAX_M, PIXEL_CONTRAST_MAX_D = 16, 1024, 4096, 256
+
+
+def _pixel_contrast_ck(what, C, K):
+    for name, v in (("C", C), ("K", K)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{what}: {name} must be an integer, given {v!r}")
+    if not 2 <= C <= PIXEL_CONTRAST_MAX_C:
+        raise ValueError(f"{what}: C = {C} classes (2 .. {PIXEL_CONTRAST_MAX_C})")
+    if not 1 <= K <= PIXEL_CONTRAST_MAX_K:
+        raise ValueError(f"{what}: K = {K} samples per class (1 .. {PIXEL_CONTRAST_MAX_K})")
+    if C * K > PIXEL_CONTRAST_MAX_M:
+        raise ValueError(f"{what}: C K = {C * K} rows (at most {PIXEL_CONTRAST_MAX_M})")
+
+
+def _pixel_seed_check(seed):
+    if isinstance(seed, torch.Tensor):
+        if seed.dtype != torch.int32 or seed.numel() != 1:
+            raise ValueError(f"pixel_sample: a seed tensor must hold one int32, given {seed.dtype} {tuple(seed.shape)}")
+    elif isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"pixel_sample: seed must be an integer in [0, 2^32) or a one-element int32 device tensor, given {seed!r}")
+
+
+def _pixel_seed_arg(seed, dev):
+    """the sampler's seed word on the device: a one-element int32 tensor as it is, a Python int in [0, 2^32) through a pinned
+    asynchronous copy (no synchronisation)"""
+    if isinstance(seed, torch.Tensor):
+        _n.require_gpu(seed)
+        if seed.device != dev:
+            raise ValueError(f"pixel_sample: the seed lies on {seed.device}, the cell labels on {dev}")
+        return seed.detach().reshape(1)
+    host = torch.tensor([seed - 2 ** 32 if seed >= 2 ** 31 else seed], dtype=torch.int32)
+    return host.pin_memory().to(dev, non_blocking=True)
+
+
+def pixel_sample(cell_label, C, K, seed):
+    """The class-balanced sample of cells (``spcl_pixel_sample``): ``cell_label`` int32 [B, h, w], a value c in [0, C) makes the
+    cell eligible for class c, anything else (-1) for none.  Per class the ``min(K, n_c)`` eligible cells with the smallest
+    keys ``fmix32(((i + 1) * 0x9E3779B1 mod 2^32) ^ seed)`` of their flat index i.  -> (``idx`` int32 [C, K]: the chosen flat
+    indices in ascending order, then -1; ``count`` int32 [C]).  ``seed``: a Python int in [0, 2^32) or a one-element int32
+    device tensor (read by the kernels, so a captured call replays with what it holds then).  A fixed number of launches,
+    nothing read back, the same bits on every run.  Bad arguments raise ``ValueError`` on the host."""
+    if not isinstance(cell_label, torch.Tensor) or cell_label.dtype != torch.int32:
+        raise ValueError(f"pixel_sample takes an int32 cell-label map, given {getattr(cell_label, 'dtype', type(cell_label).__name__)}")
+    if cell_label.dim() != 3 or min(cell_label.shape) < 1:
+        raise ValueError(f"pixel_sample: cell labels must be [B, h, w], given {tuple(cell_label.shape)}")
+    _pixel_contrast_ck("pixel_sample", C, K)
+    ncells = cell_label.numel()
+    if ncells >= 2 ** 31:
+        raise ValueError(f"pixel_sample: {ncells} cells (fewer than 2^31)")
+    _pixel_seed_check(seed)
+    _n.require_gpu(cell_label)
+    dev = cell_label.device
+    sd = _pixel_seed_arg(seed, dev)
+    cl = cell_label.detach().contiguous()
+    idx = torch.empty((C, K), dtype=torch.int32, device=dev)
+    count = torch.empty(C, dtype=torch.int32, device=dev)
+    ws = torch.empty(_n.call("spcl_pixel_sample_workspace_bytes", ncells), dtype=torch.uint8, device=dev)
+    _n.call("spcl_pixel_sample", _n.ptr(cl), ncells, C, K, _n.ptr(sd), _n.ptr(idx), _n.ptr(count), _n.ptr(ws), ws.numel(),
+            _n.stream())
+    return idx, count
+
+
+class _GatherRowsFn(torch.autograd.Function):
+    """rows[m] = feature cell idx[m] as f32 (zero rows for idx < 0), read from the map's channels-last storage in place; the
+    gradient is zero except at the chosen cells (unique indices: plain stores)"""
+
+    @staticmethod
+    def forward(ctx, feat, idx):
+        x, cs = as_nhwc(feat.detach())
+        B, h, w, _ = x.shape
+        Cf, M = feat.shape[1], idx.numel()
+        rows = torch.empty((M, Cf), dtype=torch.float32, device=feat.device)
+        _n.call("spcl_rows_gather_forward", _n.ptr(x), _n.dtype_code(x.dtype), B * h * w, Cf, cs, _n.ptr(idx), M, _n.ptr(rows),
+                _n.stream())
+        ctx.save_for_backward(idx)
+        ctx.meta = (B, h, w, Cf, cs, x.dtype, feat.dtype)
+        return rows
+
+    @staticmethod
+    def backward(ctx, drows):
+        (idx,) = ctx.saved_tensors
+        B, h, w, Cf, cs, xdt, fdt = ctx.meta
+        g = drows.detach().contiguous().float()
+        dfeat = torch.empty((B, h, w, cs), dtype=xdt, device=g.device)
+        _n.call("spcl_rows_gather_backward", _n.ptr(g), _n.ptr(idx), idx.numel(), Cf, _n.ptr(dfeat), _n.dtype_code(xdt), B * h * w,
+                cs, _n.stream())
+        gfeat = nhwc_to_logical(dfeat, Cf)
+        return (gfeat if gfeat.dtype == fdt else gfeat.to(fdt)), None
+
+
+def gather_rows(feature, idx):
+    """``rows[m, :] = feature[b, :, y, x]`` of the cell with flat index ``idx[m] = b h w + y w + x`` as f32 [idx.numel(), Cf];
+    a row whose index is -1 is exactly zero.  ``feature``: a logical [B, Cf, h, w] map, f32 or bf16 (read in place when it is
+    channels-last, padded pitch included); ``idx``: int32, any shape, its non-negative entries distinct (``pixel_sample``'s
+    are).  Differentiable in ``feature``: the gradient is zero everywhere except the chosen cells."""
+    if not isinstance(feature, torch.Tensor) or feature.dim() != 4 or feature.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("gather_rows takes a float32 or bfloat16 [B, Cf, h, w] map, given "
+                         f"{getattr(feature, 'dtype', type(feature).__name__)} {tuple(getattr(feature, 'shape', ()))}")
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or idx.numel() < 1:
+        raise ValueError(f"gather_rows: idx must be a non-empty int32 tensor, given {getattr(idx, 'dtype', type(idx).__name__)}")
+    if feature.shape[0] * feature.shape[2] * feature.shape[3] >= 2 ** 31:
+        raise ValueError(f"gather_rows: {tuple(feature.shape)} has 2^31 cells or more")
+    _n.require_gpu(feature, idx)
+    if idx.device != feature.device:
+        raise ValueError(f"gather_rows: idx on {idx.device}, the feature on {feature.device}")
+    return _GatherRowsFn.apply(feature, idx.detach().contiguous().reshape(-1))
+
+
+class _PixelSupConFn(torch.autograd.Function):
+    """``spcl_pixel_supcon_forward`` / ``_backward``: the label structure comes from ``count`` alone; the rows' log-sums stay
+    in the workspace between the two calls"""
+
+    @staticmethod
+    def forward(ctx, z, count, C, K, t):
+        zc = z.detach().contiguous()
+        M, d = zc.shape
+        dev = zc.device
+        ws = torch.empty(_n.call("spcl_pixel_supcon_workspace_bytes", M, d), dtype=torch.uint8, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _n.call("spcl_pixel_supcon_forward", _n.ptr(zc), _n.ptr(count), C, K, d, c_float(t), _n.ptr(loss), _n.ptr(ws), ws.numel(),
+                _n.stream())
+        ctx.save_for_backward(zc, count, ws)
+        ctx.meta = (C, K, d, t)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        zc, count, ws = ctx.saved_tensors
+        C, K, d, t = ctx.meta
+        gs = None if is_unit_gradient(g) else g.detach().reshape(1).float().contiguous()
+        dz = torch.empty_like(zc)
+        _n.call("spcl_pixel_supcon_backward", _n.ptr(zc), _n.ptr(count), C, K, d, c_float(t), _n.ptr(gs), _n.ptr(ws), ws.numel(),
+                _n.ptr(dz), _n.stream())
+        return dz, None, None, None, None
+
+
+def pixel_supcon(z, count, K, t=0.1):
+    """The supervised-contrastive loss of the sampled rows: ``z`` f32 [C K, d] (unit rows; 4 <= d <= 256, a multiple of 4),
+    ``count`` int32 [C] on the device.  Slot ``m = c K + j`` has class c and is valid iff ``j < count[c]``; with A(i) the valid
+    rows other than i, P(i) those of i's class and I the valid rows with a positive,
+    ``L = mean_{i in I} -(1 / |P(i)|) sum_{p in P(i)} [z_i.z_p / t - log sum_{a in A(i)} exp(z_i.z_a / t)]``, 0 for an empty
+    I.  Invalid rows are never read (NaN allowed) and get an exactly zero gradient.  Nothing is read back."""
+    if not isinstance(z, torch.Tensor) or z.dtype != torch.float32 or z.dim() != 2:
+        raise ValueError(f"pixel_supcon takes float32 [C K, d] rows, given {getattr(z, 'dtype', type(z).__name__)} "
+                         f"{tuple(getattr(z, 'shape', ()))}")
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.dim() != 1:
+        raise ValueError(f"pixel_supcon: count must be an int32 [C] tensor, given {getattr(count, 'dtype', type(count).__name__)}")
+    C = int(count.numel())
+    _pixel_contrast_ck("pixel_supcon", C, K)
+    M, d = z.shape
+    if M != C * K:
+        raise ValueError(f"pixel_supcon: {M} rows for C K = {C} x {K}")
+    if not 4 <= d <= PIXEL_CONTRAST_MAX_D or d % 4 != 0:
+        raise ValueError(f"pixel_supcon: d = {d} (4 .. {PIXEL_CONTRAST_MAX_D}, a multiple of 4)")
+    t = float(t)
+    if not t > 0.0:
+        raise ValueError(f"pixel_supcon: temperature {t} (> 0)")
+    _n.require_gpu(z, count)
+    if count.device != z.device:
+        raise ValueError(f"pixel_supcon: count on {count.device}, the rows on {z.device}")
+    return _PixelSupConFn.apply(z, count.detach().contiguous(), C, K, t)
+
+
+def pixel_contrast_labels(labels, C, size):
+    """The sampler's cell labels from label maps: ``labels`` uint8 [B, H, W] (values >= C: ignore), ``size`` = the hooked
+    feature's (h, w).  A cell keeps its majority class iff its purity is 1.0 -- every label of its pooling window is that
+    class, so boundary cells and windows with ignored pixels get -1.  -> int32 [B, h, w]."""
+    cell, purity = cell_majority(labels, C, size)
+    return torch.where(purity == 1.0, cell, -1)
+
+
 # ------------------------------------------------------------------------------------------------ mix-up (csrc/semi_reg.hip)
 class MixupPlan:
     """One mix-up draw (mixup.py:19-32) for a batch of B labelled samples and their second views: ``lam`` (the host's float64),

@@ -31,7 +31,11 @@ encoder and decoder features, one hook per estimator): the keys of config/specif
 the reference's old-API ``IICTrainer`` (trainer.py:64-95) reads from ``FeatureExtractor``.  Refused during pre-training.
 ``PseudoLabelParameters`` builds the pseudo-labelling baseline (``create_pseudo_label_hook``: FixMatch's confidence-thresholded
 self-training, optionally with FreeMatch's self-adaptive thresholds): ``weight``, ``threshold``, ``adaptive``, ``momentum``,
-``teacher`` and, for ``teacher: ema``, ``alpha`` / ``weight_decay``.  Not in the reference.  Refused during pre-training."""
+``teacher`` and, for ``teacher: ema``, ``alpha`` / ``weight_decay``.  Not in the reference.  Refused during pre-training.
+``PixelContrastParameters`` builds the label-guided pixel contrast (``create_pixel_contrast_hook``: a class-balanced sample of
+a decoder feature's cells under a supervised-contrastive criterion): ``weight``, ``feature_name``, ``samples_per_class``,
+``temperature``, ``hidden_dim``, ``output_dim``, ``head_type``, ``unlabeled_threshold`` and ``seed``.  Not in the reference.
+Refused during pre-training (it needs the labelled batch's label maps)."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -50,6 +54,7 @@ _SEMI_SECTIONS = (
     ("PICAConsistencyParams", "create_pica_consistency_hook", True, False),
     ("IICRegParameters", "create_iic_estimator_hooks", True, False),
     ("PseudoLabelParameters", "create_pseudo_label_hook", True, False),
+    ("PixelContrastParameters", "create_pixel_contrast_hook", True, False),
 )
 
 

@@ -54,7 +54,8 @@ class MixUpEpocher(SemiSupervisedEpocher):
         target = labeled_target.squeeze(1)
         sup_loss, counts = supervised_loss(self._sup_criterion, label_logits, target, self.num_classes)
         reg_loss = self.regularization(labeled_image=labeled_image, labeled_image_tf=labeled_image_tf,
-                                       labeled_target=labeled_target, labeled_target_tf=labeled_target_tf, seed=seed)
+                                       labeled_target=labeled_target, labeled_target_tf=labeled_target_tf, seed=seed,
+                                       label_logits=label_logits)
         total_loss = sup_loss + reg_loss
         if self._unit is None or self._unit.device != total_loss.device:
             self._unit = F_hip.register_unit_gradient(torch.ones((), dtype=total_loss.dtype, device=total_loss.device))

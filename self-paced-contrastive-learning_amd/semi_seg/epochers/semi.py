@@ -5,7 +5,8 @@ Same control flow, meters (``lr``, ``sup_loss``, ``sup_dice``, ``reg_loss`` + th
 regularisation keyword set (:176-187), so the InfoNCE hooks run under it as well as the UDA-IIC ones.  Two keywords are
 added for the HIP hooks: ``unlabeled_logits`` (before the flip) and ``flip_flags`` (uint8 [n] on the device: bit 0 flips H,
 bit 1 flips W -- what ``TensorRandomFlip`` draws under ``FixRandomSeed(seed)``), so the flipped copies are read by
-indexing.  The flipped second view is one ``spcl_flip_batch`` launch; the supervised loss and Dice counts are the fused
+indexing; and two for the hooks that use the labelled batch (semi_seg/hooks/pixelcontrast.py): ``labeled_target`` (the label
+maps [n_l, H, W]) and ``label_logits``.  The flipped second view is one ``spcl_flip_batch`` launch; the supervised loss and Dice counts are the fused
 launch of ``FineTuneEpocher``; model and hook parameters are one ``FlatParams`` stepped by ``FusedRAdam``, whose
 coefficient launch carries the meters' device adds.  No host synchronisation per step; eager launches (no hipGraph)."""
 import random
@@ -146,7 +147,8 @@ class SemiSupervisedEpocher(_EpocherBase):
             unlabeled_tf_logits=unlabeled_tf_logits, unlabeled_logits_tf=unlabeled_logits_tf, seed=seed,
             unlabeled_image=unlabeled_image, unlabeled_image_tf=unlabeled_image_tf, label_group=unl_group,
             partition_group=unl_partition, unlabeled_filename=unlabeled_filename, labeled_filename=labeled_filename,
-            affine_transformer=self._affine_transformer, unlabeled_logits=unlabeled_logits, flip_flags=flags)
+            affine_transformer=self._affine_transformer, unlabeled_logits=unlabeled_logits, flip_flags=flags,
+            labeled_target=target, label_logits=label_logits)
         total_loss = sup_loss + reg_loss
         if self._unit is None or self._unit.device != total_loss.device:
             self._unit = F_hip.register_unit_gradient(torch.ones((), dtype=total_loss.dtype, device=total_loss.device))

@@ -10,7 +10,8 @@ trainer-registry keys (semi_seg/trainers/__init__.py:11-12).  ``create_uc_mean_t
 ``mine``).  ``create_pica_hooks`` / ``create_pica_consistency_hook`` are the two discrete-MI factories with the PICA criteria
 (contrastyou/losses/pica_loss.py; the reference pairs them with the cluster heads in ``PICALossWrapper``,
 semi_seg/utils.py:242-263, and has no factory of its own for them).  ``create_pseudo_label_hook`` builds the pseudo-labelling
-baseline (FixMatch / FreeMatch thresholds), which the reference lacks altogether."""
+baseline (FixMatch / FreeMatch thresholds) and ``create_pixel_contrast_hook`` the label-guided pixel contrast on a decoder
+feature; the reference lacks both altogether."""
 from typing import List, Union
 
 from ...contrastyou.hooks.base import CombineTrainerHook
@@ -24,6 +25,7 @@ from .midl import MIDLPaperTrainerHook
 from .mine import MineTrainHook
 from .mt import MeanTeacherTrainerHook
 from .pica import PICATrainHook
+from .pixelcontrast import PixelContrastTrainerHook
 from .pseudolabel import PseudoLabelTrainerHook
 from .ucmt import UCMeanTeacherTrainerHook
 
@@ -164,6 +166,17 @@ def create_pseudo_label_hook(*, model, weight: float, threshold=0.95, adaptive: 
     ``alpha`` and ``weight_decay`` are the mean teacher's and matter with ``teacher="ema"`` only"""
     return PseudoLabelTrainerHook(name="pseudolabel", weight=weight, model=model, threshold=threshold, adaptive=adaptive,
                                   momentum=momentum, teacher=teacher, alpha=alpha, weight_decay=weight_decay)
+
+
+def create_pixel_contrast_hook(*, model, weight: float, feature_name: str = "Up_conv3", samples_per_class: int = 256,
+                               temperature: float = 0.1, hidden_dim: int = 128, output_dim: int = 64, head_type: str = "mlp",
+                               unlabeled_threshold=None, seed: int = 0):
+    """``PixelContrastParameters``: a class-balanced sample of the hooked feature's cells, chosen on the device by the label
+    maps, under a supervised-contrastive criterion (semi_seg/hooks/pixelcontrast.py)"""
+    return PixelContrastTrainerHook(name="pixelcontrast", model=model, feature_name=feature_name, weight=weight,
+                                    samples_per_class=samples_per_class, temperature=temperature, hidden_dim=hidden_dim,
+                                    output_dim=output_dim, head_type=head_type, unlabeled_threshold=unlabeled_threshold,
+                                    seed=seed)
 
 
 def create_entropy_min_hook(*, weight: float):
