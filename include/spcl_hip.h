@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 34
+#define SPCL_ABI_VERSION 35
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -1512,6 +1512,37 @@ int spcl_pixel_supcon_forward(const float* z, const int32_t* count, int C, int K
                               size_t ws_bytes, void* stream);
 int spcl_pixel_supcon_backward(const float* z, const int32_t* count, int C, int K, int d, float t, const float* gscale,
                                void* ws, size_t ws_bytes, float* dz, void* stream);
+
+/* ---------------------------------------------------------------- cross pseudo supervision (csrc/cross_pseudo.hip) -----------
+ * Two networks on the same images, each trained with cross-entropy towards the other's hard arg-max prediction (CPS; Chen et
+ * al., CVPR 2021); not in the reference.  Both directions in one launch.
+ *
+ *   spcl_cross_pseudo_ce: a_logits and b_logits are [N][H][W][C] f32 class maps in the same frame (no flip flags), 1 <= C <=
+ *                    16; they may be one buffer.  Per pixel: pA = softmax(a), pB = softmax(b); yA = argmax_c a_c, yB =
+ *                    argmax_c b_c on the LOGITS (exact; a tie goes to the lowest class); confA = max pA, confB = max pB, formed
+ *                    in f32 as 1 / z with z the sum of exp(logit - max logit), exactly as spcl_pseudo_label_ce forms its
+ *                    confidence; keepA = confA >= tau[yA], keepB = confB >= tau[yB] (tau: C device floats; NULL: every pixel
+ *                    with a numeric confidence is kept; a NaN confidence keeps nothing); term = keepB * -log pA[yB] + keepA *
+ *                    -log pB[yA].  With M = N H W, for a unit upstream gradient:
+ *                      loss[0] = weight / M * sum term (the mean over ALL pixels); parts[0], parts[1] = the two directions
+ *                      separately, a <- b then b <- a;
+ *                      da_k = keepB ? weight / M * (pA_k - [k == yB]) : 0,  db_k = keepA ? weight / M * (pB_k - [k == yA]) : 0
+ *                      (exact zeros at dropped pixels; the labels carry no gradient; da and db must be two buffers);
+ *                      hist [4 C + 1], exact integers: pixels per yA, pixels per yB, pixels with keepA per yA, pixels with
+ *                      keepB per yB, pixels with yA == yB;
+ *                      label_a, label_b (each may be NULL) uint8 [N][H][W]: keep ? y : 255.
+ *                    Every sum is a fixed association (per thread in pixel order, wave butterfly, waves in order, workgroup
+ *                    rows in index order by the last workgroup to take a ticket): all outputs are bitwise reproducible.  No
+ *                    floating-point atomics; ONE launch and no memset; nothing is read back.  Shapes refused: N, H or W <= 0,
+ *                    C outside [1, 16], N H W >= 2^31.  ws: spcl_cross_pseudo_workspace_bytes(N, C, H, W) bytes (0 for a
+ *                    refused shape), 8-byte aligned, ZERO-FILLED BY THE CALLER BEFORE ITS FIRST USE: it holds the ticket,
+ *                    which a completed call leaves at zero, so calls that follow one another on a stream may share it (the
+ *                    entry zeroes nothing itself: a captured memset node did not keep its value over replays).
+ *                    Captured with such a workspace that outlives the graph, every replay writes all outputs. */
+size_t spcl_cross_pseudo_workspace_bytes(int N, int C, int H, int W);
+int spcl_cross_pseudo_ce(const float* a_logits, const float* b_logits, int N, int C, int H, int W, const float* tau, float weight,
+                         float* loss, float* parts, float* da, float* db, unsigned long long* hist, uint8_t* label_a,
+                         uint8_t* label_b, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

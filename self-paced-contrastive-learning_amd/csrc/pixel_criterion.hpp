@@ -129,6 +129,65 @@ __device__ __forceinline__ void ordered_total(double v, double scale, float* __r
   }
 }
 
+// ---- criteria that hand in a ROW per workgroup: ND doubles and NC unsigned ints (cross_pseudo.hip; pseudo_label.hip, where
+// this protocol comes from, keeps its own copy and its bits).  Workgroups of 256 threads.
+__device__ __forceinline__ double wave_butterfly_sum_d(double v) {  // every lane gets the wave's sum
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// After the workgroup has stored its row: every storing wave drains its stores, one thread releases at device scope and takes
+// a ticket.  -> true in the workgroup that took the last one (uniform over the workgroup); it has fenced and may read all rows.
+__device__ __forceinline__ bool rows_take_ticket(unsigned int* __restrict__ ticket, unsigned int* s_last) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    *s_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!*s_last) return false;
+  __threadfence();
+  return true;
+}
+
+// In the closing workgroup: ncol = ND + NC columns, G = 256 / ncol groups of R = ceil(nblk / G) consecutive rows; thread
+// (group, column) adds its column over its group's rows in row order -- all of its loads independent, the whole table in flight
+// at once --, then thread `col` < ncol adds the G group sums in group order and returns with its column's total in tot (col <
+// ND) or n.  G and R follow from the grid and the column count alone: one fixed association.  s_gd, s_gc: 256 entries each.
+__device__ __forceinline__ void rows_grouped_total(const double* partial, const unsigned int* counts, int ND, int NC,
+                                                   double* s_gd, unsigned long long* s_gc, double& tot, unsigned long long& n) {
+  const int tid = threadIdx.x, nblk = (int)gridDim.x;
+  const int ncol = ND + NC, G = 256 / ncol, R = (nblk + G - 1) / G;
+  const int col = tid % ncol, grp = tid / ncol;
+  tot = 0.0;
+  n = 0ull;
+  if (grp < G) {
+    const int r0 = grp * R, r1 = r0 + R < nblk ? r0 + R : nblk;
+    if (col < ND) {
+      const volatile double* src = (const volatile double*)partial + col;
+#pragma unroll 8
+      for (int r = r0; r < r1; ++r) tot += src[(size_t)r * ND];
+    } else {
+      const volatile unsigned int* src = (const volatile unsigned int*)counts + (col - ND);
+#pragma unroll 8
+      for (int r = r0; r < r1; ++r) n += src[(size_t)r * NC];
+    }
+  }
+  s_gd[tid] = tot;
+  s_gc[tid] = n;
+  __syncthreads();
+  if (tid < ncol) {
+    tot = 0.0;
+    n = 0ull;
+    for (int g = 0; g < G; ++g) {
+      tot += s_gd[g * ncol + tid];
+      n += s_gc[g * ncol + tid];
+    }
+  }
+}
+
 // grid = ceil(M / 256) workgroups of 256.  f(pix, keep) -> the pixel's term; a functor with F::kCounts also sets `keep`, and
 // the number of kept pixels goes to kept[0] (an exact integer, summed like the terms).
 template <class F>

@@ -3830,6 +3830,88 @@ def pseudo_label_ce(teacher, student_logits, tau, weight=1.0, flags=None, state=
     return _PixelCriterionFn.apply(student_logits, launch)
 
 
+# ------------------------------------------------------------------------ cross pseudo supervision (csrc/cross_pseudo.hip)
+class _PixelCriterion2Fn(torch.autograd.Function):
+    """``_PixelCriterionFn`` for a criterion of two class maps that BOTH get a gradient: ``launch()`` returns the loss and the
+    two gradient maps [N, H, W, C] w.r.t. ``x`` and ``y`` for a unit upstream gradient.  (Given one tensor on both sides,
+    autograd adds the two maps.)"""
+
+    @staticmethod
+    def forward(ctx, x, y, launch):
+        loss, gx, gy = launch()
+        ctx.save_for_backward(gx, gy)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, gy = ctx.saved_tensors
+        if is_unit_gradient(g):
+            return gx.permute(0, 3, 1, 2), gy.permute(0, 3, 1, 2), None
+        s = g.detach().float()
+        return (gx * s).permute(0, 3, 1, 2), (gy * s).permute(0, 3, 1, 2), None
+
+
+_CROSS_PSEUDO_WS = {}
+
+
+def _cross_pseudo_workspace(nbytes, dev):
+    """The criterion's workspace for calls on the current stream of ``dev``: allocated zero-filled on first use and KEPT, one
+    per size.  The entry zeroes nothing (include/spcl_hip.h): the ticket starts at zero here and every launch leaves it at
+    zero; calls on one stream run one after the other, so they share the workspace, and a captured launch points at memory
+    that outlives its graph."""
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream, nbytes)
+    ws = _CROSS_PSEUDO_WS.get(key)
+    if ws is None:
+        ws = _CROSS_PSEUDO_WS[key] = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def cross_pseudo_ce(a_logits, b_logits, tau=None, weight=1.0, out=None):
+    """Cross pseudo supervision (Chen et al., CVPR 2021) of logical [N, C, H, W] logits of two networks on the same images, in
+    one launch: ``weight * mean over ALL pixels of [confB >= tau[yB]] * cross_entropy(a_logits, yB) + [confA >= tau[yA]] *
+    cross_entropy(b_logits, yA)`` with ``yA = argmax(a_logits)``, ``yB = argmax(b_logits)`` (the lowest class on a tie) and
+    ``conf = max softmax``, formed as ``pseudo_label_ce`` forms it.  BOTH maps get a gradient; the labels carry none.  ``tau``:
+    f32 [C] on the device, or None: every pixel is kept.  ``out`` (a list) receives ``(parts, hist, label_a, label_b)``:
+    ``parts`` f32 [2] = the two directions (a <- b, b <- a), ``hist`` int64 [4 C + 1] = (pixels per yA, pixels per yB, kept
+    pixels per yA, kept pixels per yB, pixels with yA == yB), ``label_a`` / ``label_b`` uint8 [N, H, W] = the label a network
+    teaches where it is kept and 255 elsewhere."""
+    weight = float(weight)
+
+    def launch():
+        _n.require_gpu(a_logits, b_logits)
+        as_, bs = _class_map_storage(a_logits.detach()), _class_map_storage(b_logits.detach())
+        if as_.shape != bs.shape or as_.device != bs.device:
+            raise AssertionError(f"class maps {tuple(as_.shape)} on {as_.device} / {tuple(bs.shape)} on {bs.device} differ")
+        N, H, W, C = as_.shape
+        dev = as_.device
+        if C > 16:
+            raise ValueError(f"cross_pseudo_ce: C = {C} (1 <= C <= 16)")
+        tv = None
+        if tau is not None:
+            if not isinstance(tau, torch.Tensor):
+                raise ValueError(f"cross_pseudo_ce: `tau` must be a torch.float32 [{C}] tensor on {dev}, got "
+                                 f"{type(tau).__name__}")
+            if tau.dtype != torch.float32 or tau.dim() != 1 or tau.numel() != C or tau.device != dev or not tau.is_contiguous():
+                raise ValueError(f"cross_pseudo_ce: `tau` must be a contiguous torch.float32 [{C}] tensor on {dev}: got "
+                                 f"{tau.dtype} {tuple(tau.shape)} on {tau.device}")
+            tv = tau.detach()
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        parts = torch.empty(2, dtype=torch.float32, device=dev)
+        da, db = torch.empty_like(as_), torch.empty_like(bs)
+        ws = _cross_pseudo_workspace(max(8, _n.call("spcl_cross_pseudo_workspace_bytes", N, C, H, W)), dev)
+        hist = torch.empty(4 * C + 1, dtype=torch.int64, device=dev)
+        la = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if out is not None else None
+        lb = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if out is not None else None
+        _n.call("spcl_cross_pseudo_ce", _n.ptr(as_), _n.ptr(bs), N, C, H, W, _n.ptr(tv), c_float(weight), _n.ptr(loss),
+                _n.ptr(parts), _n.ptr(da), _n.ptr(db), _n.ptr(hist), _n.ptr(la), _n.ptr(lb), _n.ptr(ws), ws.numel(),
+                _n.stream())
+        if out is not None:
+            out.extend((parts, hist, la, lb))
+        return loss, da, db
+
+    return _PixelCriterion2Fn.apply(a_logits, b_logits, launch)
+
+
 # --------------------------------------------------------------------- label-guided pixel contrast (csrc/pixel_contrast.hip)
 PIXEL_CONTRAST_MAX_C, PIXEL_CONTRAST_MAX_K, PIXEL_CONTRAST_MAX_M, PIXEL_CONTRAST_MAX_D = 16, 1024, 4096, 256
 

@@ -35,7 +35,10 @@ self-training, optionally with FreeMatch's self-adaptive thresholds): ``weight``
 ``PixelContrastParameters`` builds the label-guided pixel contrast (``create_pixel_contrast_hook``: a class-balanced sample of
 a decoder feature's cells under a supervised-contrastive criterion): ``weight``, ``feature_name``, ``samples_per_class``,
 ``temperature``, ``hidden_dim``, ``output_dim``, ``head_type``, ``unlabeled_threshold`` and ``seed``.  Not in the reference.
-Refused during pre-training (it needs the labelled batch's label maps)."""
+Refused during pre-training (it needs the labelled batch's label maps).
+``CrossPseudoParameters`` builds cross pseudo supervision (``create_cross_pseudo_hook``, hook name ``cps``: a peer network of
+the model's class, each trained towards the other's arg-max prediction): ``weight``, ``threshold``, ``peer_seed`` and ``on``.
+Not in the reference.  Refused during pre-training (the peer's own objective is the supervised loss)."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -55,6 +58,7 @@ _SEMI_SECTIONS = (
     ("IICRegParameters", "create_iic_estimator_hooks", True, False),
     ("PseudoLabelParameters", "create_pseudo_label_hook", True, False),
     ("PixelContrastParameters", "create_pixel_contrast_hook", True, False),
+    ("CrossPseudoParameters", "create_cross_pseudo_hook", True, False),
 )
 
 

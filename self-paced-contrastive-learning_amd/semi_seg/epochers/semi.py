@@ -104,19 +104,22 @@ class SemiSupervisedEpocher(_EpocherBase):
             return total
         return torch.zeros((), dtype=torch.float, device=self._device)
 
-    def _bn_context(self):
+    def _bn_context(self, model=None):
         """``_disable_tracking_bn_stats`` (new_epocher.py:225-227): batch statistics, running statistics left alone"""
-        return self._model.set_bn_track(False) if self._disable_bn else nullcontext()
+        model = self._model if model is None else model
+        return model.set_bn_track(False) if self._disable_bn else nullcontext()
 
-    def _forward_pass(self, labeled_image, unlabeled_image, unlabeled_image_tf):  # new_epocher.py:205-222
+    def _forward_pass(self, labeled_image, unlabeled_image, unlabeled_image_tf, model=None):  # new_epocher.py:205-222
+        """``model``: another network to run under the same policy (semi_seg/hooks/cps.py runs its peer); default the model"""
+        model = self._model if model is None else model
         n_l, n_unl = len(labeled_image), len(unlabeled_image)
         if not self._two_stage:
-            logits = self._model(torch.cat([labeled_image, unlabeled_image, unlabeled_image_tf], dim=0))
+            logits = model(torch.cat([labeled_image, unlabeled_image, unlabeled_image_tf], dim=0))
             return torch.split(logits, [n_l, n_unl, n_unl], dim=0)
-        label_logits = self._model(labeled_image)
-        with self._bn_context():
+        label_logits = model(labeled_image)
+        with self._bn_context(model):
             unlabeled_logits, unlabeled_tf_logits = torch.split(
-                self._model(torch.cat([unlabeled_image, unlabeled_image_tf], dim=0)), [n_unl, n_unl], dim=0)
+                model(torch.cat([unlabeled_image, unlabeled_image_tf], dim=0)), [n_unl, n_unl], dim=0)
         return label_logits, unlabeled_logits, unlabeled_tf_logits
 
     def flip_flags(self, seed, n):

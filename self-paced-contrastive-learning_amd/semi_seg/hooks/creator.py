@@ -11,12 +11,14 @@ trainer-registry keys (semi_seg/trainers/__init__.py:11-12).  ``create_uc_mean_t
 (contrastyou/losses/pica_loss.py; the reference pairs them with the cluster heads in ``PICALossWrapper``,
 semi_seg/utils.py:242-263, and has no factory of its own for them).  ``create_pseudo_label_hook`` builds the pseudo-labelling
 baseline (FixMatch / FreeMatch thresholds) and ``create_pixel_contrast_hook`` the label-guided pixel contrast on a decoder
-feature; the reference lacks both altogether."""
+feature; ``create_cross_pseudo_hook`` builds cross pseudo supervision with a peer network; the reference lacks all three
+altogether."""
 from typing import List, Union
 
 from ...contrastyou.hooks.base import CombineTrainerHook
 from ..arch.unet import sort_arch
 from .consistency import ConsistencyTrainerHook
+from .cps import CrossPseudoTrainerHook
 from .discretemi import DiscreteMITrainHook
 from .entmin import EntropyMinTrainerHook
 from .iic_estimator import IICEstimatorTrainHook
@@ -177,6 +179,13 @@ def create_pixel_contrast_hook(*, model, weight: float, feature_name: str = "Up_
                                     samples_per_class=samples_per_class, temperature=temperature, hidden_dim=hidden_dim,
                                     output_dim=output_dim, head_type=head_type, unlabeled_threshold=unlabeled_threshold,
                                     seed=seed)
+
+
+def create_cross_pseudo_hook(*, model, weight: float, threshold=0.0, peer_seed: int = 1,
+                             on=("labeled", "unlabeled", "unlabeled_tf")):
+    """``CrossPseudoParameters``: cross pseudo supervision with a peer network of the model's class, initialised under
+    ``peer_seed`` (semi_seg/hooks/cps.py); ``threshold`` 0 is plain CPS, ``on`` names the class maps the cross term covers"""
+    return CrossPseudoTrainerHook(name="cps", weight=weight, model=model, threshold=threshold, peer_seed=peer_seed, on=on)
 
 
 def create_entropy_min_hook(*, weight: float):

@@ -57,6 +57,19 @@ def _dense_run(tensors):
     return first.as_strided((total,), (1,))
 
 
+def compute_dtype_pairs(student: nn.Module, other: nn.Module):
+    """the (student module, other module) pairs that carry a compute dtype, for two networks of one class"""
+    return [(s, t) for s, t in zip(student.modules(), other.modules())
+            if "_compute_dtype" in s.__dict__ or hasattr(type(s), "_compute_dtype")]
+
+
+def match_compute_dtype(pairs):
+    """give the second network of every pair the compute dtype its student has now (also used by cps.py for its peer)"""
+    for s, t in pairs:
+        if t._compute_dtype != s._compute_dtype:
+            t._compute_dtype = s._compute_dtype
+
+
 class MeanTeacherTrainerHook(TrainerHook):
 
     def __init__(self, name: str, weight: float, model: nn.Module, alpha: float = 0.999, weight_decay: float = 1e-5,
@@ -129,11 +142,8 @@ class _MeanTeacherEpocherHook(EpocherHook):
 
     def _match_compute_dtype(self, student):
         if self._dtype_pairs is None:
-            self._dtype_pairs = [(s, t) for s, t in zip(student.modules(), self._teacher_model.modules())
-                                 if "_compute_dtype" in s.__dict__ or hasattr(type(s), "_compute_dtype")]
-        for s, t in self._dtype_pairs:
-            if t._compute_dtype != s._compute_dtype:
-                t._compute_dtype = s._compute_dtype
+            self._dtype_pairs = compute_dtype_pairs(student, self._teacher_model)
+        match_compute_dtype(self._dtype_pairs)
 
     @meter_focus
     def __call__(self, *, unlabeled_tf_logits, unlabeled_image, seed, affine_transformer, flip_flags=None, **kwargs):
