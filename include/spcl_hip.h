@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 35
+#define SPCL_ABI_VERSION 36
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -1543,6 +1543,64 @@ size_t spcl_cross_pseudo_workspace_bytes(int N, int C, int H, int W);
 int spcl_cross_pseudo_ce(const float* a_logits, const float* b_logits, int N, int C, int H, int W, const float* tau, float weight,
                          float* loss, float* parts, float* da, float* db, unsigned long long* hist, uint8_t* label_a,
                          uint8_t* label_b, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- CutMix for cross pseudo supervision (csrc/cutmix.hip) -------
+ * The strong perturbation of CPS + CutMix (French et al., BMVC 2020; Chen et al., CVPR 2021), ABI 36; not in the reference.  One
+ * box per sample, drawn on the device; inside box n the mixed sample n shows sample src = (n + roll) mod N, elsewhere itself.
+ * Nothing is read back, every entry is one capturable launch, all outputs are bitwise reproducible, no floating-point atomics.
+ *
+ *   spcl_cutmix_boxes: boxes int32 [N][4] = (y0, x0, bh, bw): rows [y0, y0 + bh), columns [x0, x0 + bw) of an H x W image.
+ *                    seed: ONE 32-bit word in device memory (read by the kernel: a captured call replays with what the word
+ *                    holds then).  lo16 <= hi16: the range of the box's share of the image area in units of 1 / 65536.  With
+ *                    key(i) = fmix32((((i + 1) * 0x9E3779B1) mod 2^32) ^ *seed) (spcl_pixel_sample's key), integers only and
+ *                    every product in 64 bits:
+ *                      r_j = key(4 n + j), j = 0 .. 3;  u_j = r_j >> 8
+ *                      P = lo16 + (((hi16 - lo16) * u_0) >> 24)                        the area share
+ *                      S = P + (((65536 - P) * u_1) >> 24);  T = (P * 65536) / S       the two side shares, S T ~ P 65536
+ *                      (sh, sw) = (r_1 & 1) ? (S, T) : (T, S)
+ *                      bh = min(H, max(1, (H * sh + 32768) >> 16));  bw = min(W, max(1, (W * sw + 32768) >> 16))
+ *                      y0 = ((H - bh + 1) * u_2) >> 24;  x0 = ((W - bw + 1) * u_3) >> 24
+ *                    (French et al.'s generator with a linear-uniform side share in place of the log-uniform one: no exp or
+ *                    log, so a host restatement is exact; the fair bit r_1 & 1 keeps height and width symmetric.)  Every box
+ *                    lies inside its image.  Refused: a null pointer, N outside [1, 2^20], H or W <= 0, not 1 <= lo16 <= hi16
+ *                    <= 65536.
+ *   spcl_cutmix_images: out[n][..][h][w] = x[src(n, h, w)][..][h][w], src = (n + roll) mod N inside box n and n elsewhere: a
+ *                    pure copy (bit-identical to a select between x and its roll).  dtype SPCL_F32 / SPCL_BF16; channels_last
+ *                    == 0: x and out are contiguous [N][C][H][W], else [N][H][W][C].  16-byte accesses where the contiguous
+ *                    run of an image row (W, or W C, elements) is a multiple of 16 bytes and both pointers are aligned.
+ *                    Refused: a null pointer, a bad dtype, a non-positive extent, N C H W >= 2^31, out == x (an in-place
+ *                    gather races), roll outside [1, N - 1].  No index is formed from a box value.
+ *   spcl_cross_pseudo_ce_mixed: spcl_cross_pseudo_ce with the labels read through the boxes.  s_a, s_b: the two networks'
+ *                    logits on the MIXED images (they get the gradients da, db); t_a, t_b: their logits on the UNMIXED images
+ *                    (constants); all four [N][H][W][C] f32, 1 <= C <= 16.  Per pixel (n, h, w) with m = src(n, h, w)
+ *                    (boxes NULL: m = n, roll ignored):
+ *                      yA = argmax_c t_a[m][h][w][c] (lowest class on a tie), confA = max softmax(t_a[m][h][w]) formed as
+ *                      spcl_cross_pseudo_ce forms it (the same helper, the same bits), keepA = confA >= tau[yA] (tau NULL:
+ *                      every numeric confidence keeps); yB, confB, keepB likewise from t_b;
+ *                      term = keepB * -log softmax(s_a[n][h][w])[yB] + keepA * -log softmax(s_b[n][h][w])[yA];
+ *                      loss[0] = weight / M * sum term, M = N H W; parts[0], parts[1] the two directions (s_a <- t_b, s_b <-
+ *                      t_a); da = keepB ? weight / M * (softmax(s_a) - onehot(yB)) : 0, db likewise with keepA, yA (exact
+ *                      zeros at dropped pixels; da and db must be two buffers);
+ *                      hist [4 C + 2], exact integers: pixels per yA, pixels per yB, pixels with keepA per yA, pixels with
+ *                      keepB per yB, pixels with yA == yB, pixels inside a box;
+ *                      label_a, label_b (each may be NULL) uint8 [N][H][W] in the MIXED frame: keep ? y : 255.
+ *                    (Mixing the teachers' logits with the binary mask and then taking the arg-max, as the official
+ *                    implementation does, is this selection.)  Each map is read once, each soft-max formed once, no mixed
+ *                    teacher map is written.  Sums in spcl_cross_pseudo_ce's association: with boxes NULL, t_a == s_a and
+ *                    t_b == s_b every output is that entry's, bit for bit.  The sample read is n or (n + roll) mod N whatever
+ *                    the boxes hold (unsigned range compares).  Refused: a null pointer, C outside [1, 16], N, H or W <= 0,
+ *                    N H W >= 2^31, da == db, a short or not 8-byte aligned workspace and, with boxes given, roll outside
+ *                    [1, N - 1] (so N >= 2).  ws: spcl_cross_pseudo_mixed_workspace_bytes(N, C, H, W) bytes (0 for a refused
+ *                    shape), ZERO-FILLED BY THE CALLER BEFORE ITS FIRST USE and left with its ticket at zero by every
+ *                    completed call, as spcl_cross_pseudo_ce's; ONE launch and no memset. */
+int spcl_cutmix_boxes(const uint32_t* seed, int N, int H, int W, int lo16, int hi16, int32_t* boxes, void* stream);
+int spcl_cutmix_images(const void* x, void* out, int dtype, int N, int C, int H, int W, int channels_last, const int32_t* boxes,
+                       int roll, void* stream);
+size_t spcl_cross_pseudo_mixed_workspace_bytes(int N, int C, int H, int W);
+int spcl_cross_pseudo_ce_mixed(const float* s_a, const float* s_b, const float* t_a, const float* t_b, int N, int C, int H, int W,
+                               const int32_t* boxes, int roll, const float* tau, float weight, float* loss, float* parts,
+                               float* da, float* db, unsigned long long* hist, uint8_t* label_a, uint8_t* label_b, void* ws,
+                               size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

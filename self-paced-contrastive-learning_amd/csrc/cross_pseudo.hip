@@ -45,37 +45,7 @@ struct cps_args {
   int C;
 };
 
-// the arg-max of the logits (strictly greater: a tie stays with the lower class)
-__device__ __forceinline__ int argmax_logits(const float (&x)[16], int C) {
-  int y = 0;
-  float best = x[0];
-#pragma unroll
-  for (int k = 1; k < 16; ++k)
-    if (k < C && x[k] > best) {
-      best = x[k];
-      y = k;
-    }
-  return y;
-}
-
-// one direction of a kept pixel: x holds the learner's logits, y the other network's label.  -> -log softmax(x)_y, with no
-// quotient that could underflow; g <- gs * (softmax(x) - onehot(y)).  Dropped: 0 and exact zeros.
-template <int CT>
-__device__ __forceinline__ double cross_term(float (&x)[16], float z, float m, float xy, int y, bool keep, float gs, int C,
-                                             float* __restrict__ dst) {
-  float g[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) g[k] = 0.f;
-  double term = 0.0;
-  if (keep) {
-    term = (double)(logf(z) - (xy - m));
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < C) g[k] = gs * (x[k] / z - (k == y ? 1.f : 0.f));
-  }
-  store_pixel<CT>(dst, C, g);
-  return term;
-}
+// (argmax_logits, cross_term: pixel_criterion.hpp, shared with cutmix.hip)
 
 // CT = 4: C == 4 and the four maps 16-byte aligned (vector accesses); CT = 0: any C <= 16
 template <int CT>

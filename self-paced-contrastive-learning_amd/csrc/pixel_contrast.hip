@@ -32,22 +32,13 @@
 #include <limits.h>
 #include <algorithm>
 #include "common.hpp"
+#include "pixel_key.hpp"
 
 namespace spcl {
 
 constexpr int PXC_MAX_C = 16, PXC_MAX_K = 1024, PXC_MAX_M = 4096, PXC_MAX_D = 256;
 constexpr int PXS_MAX_UNITS = 1024;  // waves of the count / write launches (four per workgroup)
-constexpr int PXS_HIST_WORDS = 4 * PXC_MAX_C * 256;
-
-__device__ __forceinline__ uint32_t pxs_key(uint32_t i, uint32_t seed) {
-  uint32_t h = ((i + 1u) * 0x9E3779B1u) ^ seed;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
+constexpr int PXS_HIST_WORDS = 4 * PXC_MAX_C * 256;  // (pxs_key: pixel_key.hpp, shared with cutmix.hip)
 
 struct PxsWs {
   uint32_t* hist;     // [4][16][256], zero on entry

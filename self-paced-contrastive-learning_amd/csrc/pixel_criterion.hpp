@@ -129,8 +129,8 @@ __device__ __forceinline__ void ordered_total(double v, double scale, float* __r
   }
 }
 
-// ---- criteria that hand in a ROW per workgroup: ND doubles and NC unsigned ints (cross_pseudo.hip; pseudo_label.hip, where
-// this protocol comes from, keeps its own copy and its bits).  Workgroups of 256 threads.
+// ---- criteria that hand in a ROW per workgroup: ND doubles and NC unsigned ints (cross_pseudo.hip, cutmix.hip;
+// pseudo_label.hip, where this protocol comes from, keeps its own copy and its bits).  Workgroups of 256 threads.
 __device__ __forceinline__ double wave_butterfly_sum_d(double v) {  // every lane gets the wave's sum
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -156,13 +156,22 @@ __device__ __forceinline__ bool rows_take_ticket(unsigned int* __restrict__ tick
 // (group, column) adds its column over its group's rows in row order -- all of its loads independent, the whole table in flight
 // at once --, then thread `col` < ncol adds the G group sums in group order and returns with its column's total in tot (col <
 // ND) or n.  G and R follow from the grid and the column count alone: one fixed association.  s_gd, s_gc: 256 entries each.
-__device__ __forceinline__ void rows_grouped_total(const double* partial, const unsigned int* counts, int ND, int NC,
-                                                   double* s_gd, unsigned long long* s_gc, double& tot, unsigned long long& n) {
+//
+// EXTRA (cutmix.hip): a row holds one more integer behind its NC (row pitch NC + 1) that does NOT enter the column count, so
+// the groups -- and with them the association of the double sums -- stay those of the NC-column criterion; the thread of the
+// last column adds it beside its own and returns its total in `extra` (s_ge: 256 entries).  Integer sums do not depend on the
+// grouping.  Without EXTRA the code is what it was.
+template <bool EXTRA>
+__device__ __forceinline__ void rows_grouped_total_x(const double* partial, const unsigned int* counts, int ND, int NC,
+                                                     double* s_gd, unsigned long long* s_gc, unsigned long long* s_ge, double& tot,
+                                                     unsigned long long& n, unsigned long long& extra) {
   const int tid = threadIdx.x, nblk = (int)gridDim.x;
   const int ncol = ND + NC, G = 256 / ncol, R = (nblk + G - 1) / G;
+  const int pitch = EXTRA ? NC + 1 : NC;
   const int col = tid % ncol, grp = tid / ncol;
   tot = 0.0;
   n = 0ull;
+  extra = 0ull;
   if (grp < G) {
     const int r0 = grp * R, r1 = r0 + R < nblk ? r0 + R : nblk;
     if (col < ND) {
@@ -172,20 +181,66 @@ __device__ __forceinline__ void rows_grouped_total(const double* partial, const 
     } else {
       const volatile unsigned int* src = (const volatile unsigned int*)counts + (col - ND);
 #pragma unroll 8
-      for (int r = r0; r < r1; ++r) n += src[(size_t)r * NC];
+      for (int r = r0; r < r1; ++r) n += src[(size_t)r * pitch];
+      if (EXTRA && col == ncol - 1) {
+#pragma unroll 8
+        for (int r = r0; r < r1; ++r) extra += src[(size_t)r * pitch + 1];
+      }
     }
   }
   s_gd[tid] = tot;
   s_gc[tid] = n;
+  if (EXTRA) s_ge[tid] = extra;
   __syncthreads();
   if (tid < ncol) {
     tot = 0.0;
     n = 0ull;
+    extra = 0ull;
     for (int g = 0; g < G; ++g) {
       tot += s_gd[g * ncol + tid];
       n += s_gc[g * ncol + tid];
+      if (EXTRA) extra += s_ge[g * ncol + tid];
     }
   }
+}
+
+__device__ __forceinline__ void rows_grouped_total(const double* partial, const unsigned int* counts, int ND, int NC,
+                                                   double* s_gd, unsigned long long* s_gc, double& tot, unsigned long long& n) {
+  unsigned long long extra;
+  rows_grouped_total_x<false>(partial, counts, ND, NC, s_gd, s_gc, nullptr, tot, n, extra);
+}
+
+// the arg-max of C <= 16 logits (strictly greater: a tie stays with the lower class)
+__device__ __forceinline__ int argmax_logits(const float (&x)[16], int C) {
+  int y = 0;
+  float best = x[0];
+#pragma unroll
+  for (int k = 1; k < 16; ++k)
+    if (k < C && x[k] > best) {
+      best = x[k];
+      y = k;
+    }
+  return y;
+}
+
+// one direction of the cross pseudo supervision of a kept pixel (after softmax_numerators(x) -> z; m = max x, xy = x_y taken
+// BEFORE): x holds the learner's logits, y the other network's label.  -> -log softmax(x)_y, with no
+// quotient that could underflow; g <- gs * (softmax(x) - onehot(y)).  Dropped: 0 and exact zeros.
+template <int CT>
+__device__ __forceinline__ double cross_term(float (&x)[16], float z, float m, float xy, int y, bool keep, float gs, int C,
+                                             float* __restrict__ dst) {
+  float g[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) g[k] = 0.f;
+  double term = 0.0;
+  if (keep) {
+    term = (double)(logf(z) - (xy - m));
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < C) g[k] = gs * (x[k] / z - (k == y ? 1.f : 0.f));
+  }
+  store_pixel<CT>(dst, C, g);
+  return term;
 }
 
 // grid = ceil(M / 256) workgroups of 256.  f(pix, keep) -> the pixel's term; a functor with F::kCounts also sets `keep`, and

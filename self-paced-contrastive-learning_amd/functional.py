@@ -3854,12 +3854,16 @@ class _PixelCriterion2Fn(torch.autograd.Function):
 _CROSS_PSEUDO_WS = {}
 
 
-def _cross_pseudo_workspace(nbytes, dev):
+def _cross_pseudo_workspace(nbytes, dev, layout):
     """The criterion's workspace for calls on the current stream of ``dev``: allocated zero-filled on first use and KEPT, one
-    per size.  The entry zeroes nothing (include/spcl_hip.h): the ticket starts at zero here and every launch leaves it at
-    zero; calls on one stream run one after the other, so they share the workspace, and a captured launch points at memory
-    that outlives its graph."""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream, nbytes)
+    per LAYOUT and size.  The entry zeroes nothing (include/spcl_hip.h): the ticket starts at zero here and every launch
+    leaves it at zero; calls on one stream run one after the other, so they share the workspace, and a captured launch points
+    at memory that outlives its graph.  ``layout`` = (entry, C): the ticket lies behind the rows of doubles, at an offset that
+    depends on the number of workgroups, and two layouts can ask for the same number of bytes (``cross_pseudo_ce`` on 22 x 4 x
+    32 x 32 and ``cross_pseudo_ce_mixed`` on 21 x 4 x 32 x 32: 1912 bytes each; one entry at C = 2 with 17 workgroups and at C = 3
+    with 13: 948 bytes each) -- a buffer one layout has used holds partial sums where the other expects its zero ticket.  Entry,
+    C and size together fix the number of workgroups, so one buffer only ever sees one layout."""
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream, nbytes, layout)
     ws = _CROSS_PSEUDO_WS.get(key)
     if ws is None:
         ws = _CROSS_PSEUDO_WS[key] = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
@@ -3898,7 +3902,7 @@ def cross_pseudo_ce(a_logits, b_logits, tau=None, weight=1.0, out=None):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         parts = torch.empty(2, dtype=torch.float32, device=dev)
         da, db = torch.empty_like(as_), torch.empty_like(bs)
-        ws = _cross_pseudo_workspace(max(8, _n.call("spcl_cross_pseudo_workspace_bytes", N, C, H, W)), dev)
+        ws = _cross_pseudo_workspace(max(8, _n.call("spcl_cross_pseudo_workspace_bytes", N, C, H, W)), dev, ("cps", C))
         hist = torch.empty(4 * C + 1, dtype=torch.int64, device=dev)
         la = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if out is not None else None
         lb = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if out is not None else None
@@ -3910,6 +3914,154 @@ def cross_pseudo_ce(a_logits, b_logits, tau=None, weight=1.0, out=None):
         return loss, da, db
 
     return _PixelCriterion2Fn.apply(a_logits, b_logits, launch)
+
+
+# ------------------------------------------------------------------- CutMix for cross pseudo supervision (csrc/cutmix.hip)
+CUTMIX_MAX_N = 1 << 20
+
+
+def _cutmix_share16(prop_range, what):
+    """``prop_range = (lo, hi)``, the box's share of the image area, in the kernel's units of 1 / 65536"""
+    try:
+        lo, hi = (float(v) for v in prop_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: prop_range must be a pair (lo, hi), given {prop_range!r}") from None
+    if not 0.0 < lo <= hi <= 1.0:
+        raise ValueError(f"{what}: prop_range ({lo}, {hi}) must satisfy 0 < lo <= hi <= 1")
+    lo16, hi16 = int(round(lo * 65536)), int(round(hi * 65536))
+    if not 1 <= lo16 <= hi16 <= 65536:
+        raise ValueError(f"{what}: prop_range ({lo}, {hi}) is below the rule's resolution of 1 / 65536")
+    return lo16, hi16
+
+
+def _cutmix_boxes_arg(boxes, N, dev, what):
+    if not isinstance(boxes, torch.Tensor):
+        raise ValueError(f"{what}: `boxes` must be a torch.int32 [{N}, 4] tensor on {dev}, got {type(boxes).__name__}")
+    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (N, 4) or boxes.device != dev:
+        raise ValueError(f"{what}: `boxes` must be a torch.int32 [{N}, 4] tensor on {dev}: got {boxes.dtype} "
+                         f"{tuple(boxes.shape)} on {boxes.device}")
+    return boxes.detach().contiguous()
+
+
+def _cutmix_roll_arg(roll, N, what):
+    if isinstance(roll, bool) or not isinstance(roll, int) or not 1 <= roll <= N - 1:
+        raise ValueError(f"{what}: roll = {roll!r} for {N} samples (an integer in 1 .. N - 1: the mix needs two samples)")
+    return roll
+
+
+def cutmix_boxes(seed, N, H, W, prop_range=(0.25, 0.5), device=None):
+    """One CutMix box per sample (``spcl_cutmix_boxes``, one launch) -> int32 [N, 4] = ``(y0, x0, bh, bw)``: rows ``[y0, y0 +
+    bh)``, columns ``[x0, x0 + bw)`` of an H x W image.  The box's share of the area is uniform in ``prop_range``, its aspect
+    ratio follows French et al.'s generator with a linear-uniform side share and a fair bit for tall / wide (include/spcl_hip.h
+    states the integer rule; tests/_cutmix_oracle.py restates it exactly).  ``seed``: a Python int in [0, 2^32) or a one-element
+    int32 device tensor (read by the kernel, so a captured call replays with what it holds then), as ``pixel_sample``'s.
+    Nothing is read back; the same bits on every run.  Bad arguments raise ``ValueError`` on the host."""
+    for name, v in (("N", N), ("H", H), ("W", W)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"cutmix_boxes: {name} must be a positive integer, given {v!r}")
+    if N > CUTMIX_MAX_N:
+        raise ValueError(f"cutmix_boxes: N = {N} samples (at most {CUTMIX_MAX_N})")
+    lo16, hi16 = _cutmix_share16(prop_range, "cutmix_boxes")
+    _pixel_seed_check(seed)
+    if device is not None:
+        dev = torch.device(device)
+    elif isinstance(seed, torch.Tensor):
+        dev = seed.device
+    else:
+        dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    if dev.type != "cuda":
+        _n.require_gpu(torch.empty(0, device=dev))  # (raises: there is no CPU path)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    sd = _pixel_seed_arg(seed, dev)
+    boxes = torch.empty((N, 4), dtype=torch.int32, device=dev)
+    _n.call("spcl_cutmix_boxes", _n.ptr(sd), N, H, W, lo16, hi16, _n.ptr(boxes), _n.stream())
+    return boxes
+
+
+def cutmix_images(x, boxes, roll=1):
+    """The box-wise image mix (``spcl_cutmix_images``, one launch): ``out[n, :, h, w] = x[(n + roll) % N, :, h, w]`` inside box
+    ``n`` and ``x[n, :, h, w]`` elsewhere -- ``torch.where(mask, x.roll(-roll, 0), x)``, bit for bit.  ``x``: [N, C, H, W], f32
+    or bf16, contiguous or channels-last (the result has ``x``'s layout; any other striding is made contiguous first).
+    ``boxes``: int32 [N, 4] on ``x``'s device (``cutmix_boxes``); their values steer the selection only, never an address.  No
+    autograd: images carry no gradient."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16) or x.numel() == 0:
+        raise ValueError("cutmix_images takes a non-empty float32 or bfloat16 [N, C, H, W] batch, given "
+                         f"{getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}")
+    _n.require_gpu(x)
+    N, C, H, W = x.shape
+    if x.numel() >= 2 ** 31:
+        raise ValueError(f"cutmix_images: {tuple(x.shape)} has 2^31 elements or more")
+    bx = _cutmix_boxes_arg(boxes, N, x.device, "cutmix_images")
+    roll = _cutmix_roll_arg(roll, N, "cutmix_images")
+    src = x.detach()
+    if src.is_contiguous():
+        cl = 0
+    elif src.is_contiguous(memory_format=torch.channels_last):
+        cl = 1
+    else:
+        src, cl = src.contiguous(), 0
+    out = torch.empty_like(src, memory_format=torch.channels_last if cl else torch.contiguous_format)
+    _n.call("spcl_cutmix_images", _n.ptr(src), _n.ptr(out), _n.dtype_code(src.dtype), N, C, H, W, cl, _n.ptr(bx), roll,
+            _n.stream())
+    return out
+
+
+def cross_pseudo_ce_mixed(s_a, s_b, t_a, t_b, boxes=None, roll=1, tau=None, weight=1.0, out=None):
+    """Cross pseudo supervision under CutMix in one launch (``spcl_cross_pseudo_ce_mixed``).  ``s_a`` / ``s_b``: the two
+    networks' logits on the MIXED images (``cutmix_images``), both get a gradient; ``t_a`` / ``t_b``: their logits on the UNMIXED
+    images, constants (detached here).  All four logical [N, C, H, W].  Pixel ``(n, h, w)`` takes its labels from the teachers'
+    pixel ``(m, h, w)``, ``m = (n + roll) % N`` inside box ``n`` and ``n`` elsewhere (``boxes`` None: ``m = n``, ``roll`` is not
+    looked at): ``weight * mean over ALL pixels of [confB >= tau[yB]] * cross_entropy(s_a, yB) + [confA >= tau[yA]] *
+    cross_entropy(s_b, yA)`` with ``yA = argmax(t_a[m])``, ``confA = max softmax(t_a[m])`` formed as ``cross_pseudo_ce`` and
+    ``pseudo_label_ce`` form it, likewise B.  No mixed teacher map is built.  ``tau``: f32 [C] on the device, or None: every
+    pixel is kept.  ``out`` (a list) receives ``(parts, hist, label_a, label_b)``: ``parts`` f32 [2] = the two directions (s_a
+    <- t_b, s_b <- t_a), ``hist`` int64 [4 C + 2] = (pixels per yA, pixels per yB, kept pixels per yA, kept pixels per yB,
+    pixels with yA == yB, pixels inside a box), ``label_a`` / ``label_b`` uint8 [N, H, W] in the mixed frame = the label a
+    teacher gives where it is kept and 255 elsewhere."""
+    weight = float(weight)
+
+    def launch():
+        _n.require_gpu(s_a, s_b, t_a, t_b)
+        maps = [_class_map_storage(t.detach()) for t in (s_a, s_b, t_a, t_b)]
+        sas, sbs, tas, tbs = maps
+        for other in maps[1:]:
+            if other.shape != sas.shape or other.device != sas.device:
+                raise AssertionError(f"class maps {tuple(sas.shape)} on {sas.device} / {tuple(other.shape)} on {other.device} "
+                                     "differ")
+        N, H, W, C = sas.shape
+        dev = sas.device
+        if C > 16:
+            raise ValueError(f"cross_pseudo_ce_mixed: C = {C} (1 <= C <= 16)")
+        tv = None
+        if tau is not None:
+            if not isinstance(tau, torch.Tensor):
+                raise ValueError(f"cross_pseudo_ce_mixed: `tau` must be a torch.float32 [{C}] tensor on {dev}, got "
+                                 f"{type(tau).__name__}")
+            if tau.dtype != torch.float32 or tau.dim() != 1 or tau.numel() != C or tau.device != dev or not tau.is_contiguous():
+                raise ValueError(f"cross_pseudo_ce_mixed: `tau` must be a contiguous torch.float32 [{C}] tensor on {dev}: got "
+                                 f"{tau.dtype} {tuple(tau.shape)} on {tau.device}")
+            tv = tau.detach()
+        bx, r = None, 0
+        if boxes is not None:
+            bx = _cutmix_boxes_arg(boxes, N, dev, "cross_pseudo_ce_mixed")
+            r = _cutmix_roll_arg(roll, N, "cross_pseudo_ce_mixed")
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        parts = torch.empty(2, dtype=torch.float32, device=dev)
+        da, db = torch.empty_like(sas), torch.empty_like(sbs)
+        ws = _cross_pseudo_workspace(max(8, _n.call("spcl_cross_pseudo_mixed_workspace_bytes", N, C, H, W)), dev,
+                                      ("cps_mixed", C))
+        hist = torch.empty(4 * C + 2, dtype=torch.int64, device=dev)
+        la = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if out is not None else None
+        lb = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if out is not None else None
+        _n.call("spcl_cross_pseudo_ce_mixed", _n.ptr(sas), _n.ptr(sbs), _n.ptr(tas), _n.ptr(tbs), N, C, H, W, _n.ptr(bx), r,
+                _n.ptr(tv), c_float(weight), _n.ptr(loss), _n.ptr(parts), _n.ptr(da), _n.ptr(db), _n.ptr(hist), _n.ptr(la),
+                _n.ptr(lb), _n.ptr(ws), ws.numel(), _n.stream())
+        if out is not None:
+            out.extend((parts, hist, la, lb))
+        return loss, da, db
+
+    return _PixelCriterion2Fn.apply(s_a, s_b, launch)
 
 
 # --------------------------------------------------------------------- label-guided pixel contrast (csrc/pixel_contrast.hip)

@@ -37,7 +37,8 @@ a decoder feature's cells under a supervised-contrastive criterion): ``weight``,
 ``temperature``, ``hidden_dim``, ``output_dim``, ``head_type``, ``unlabeled_threshold`` and ``seed``.  Not in the reference.
 Refused during pre-training (it needs the labelled batch's label maps).
 ``CrossPseudoParameters`` builds cross pseudo supervision (``create_cross_pseudo_hook``, hook name ``cps``: a peer network of
-the model's class, each trained towards the other's arg-max prediction): ``weight``, ``threshold``, ``peer_seed`` and ``on``.
+the model's class, each trained towards the other's arg-max prediction): ``weight``, ``threshold``, ``peer_seed``, ``on`` and
+``cutmix`` (``{prop_range, seed}``; with ``"cutmix"`` in ``on`` the hook adds the CutMix term on a box-mixed unlabelled batch).
 Not in the reference.  Refused during pre-training (the peer's own objective is the supervised loss)."""
 from .semi_seg import hooks as _hooks
 

@@ -122,6 +122,16 @@ class SemiSupervisedEpocher(_EpocherBase):
                 model(torch.cat([unlabeled_image, unlabeled_image_tf], dim=0)), [n_unl, n_unl], dim=0)
         return label_logits, unlabeled_logits, unlabeled_tf_logits
 
+    def _forward_unlabeled(self, image, model=None):
+        """one network on ONE unlabelled batch under the policy of ``_forward_pass``'s unlabelled stage: with ``two_stage``
+        inside ``_bn_context`` (``disable_bn`` holds for any network), else a plain pass.  For hooks that run forwards of their
+        own on images they made (semi_seg/hooks/cps.py runs the model and its peer on the CutMix batch)."""
+        model = self._model if model is None else model
+        if not self._two_stage:
+            return model(image)
+        with self._bn_context(model):
+            return model(image)
+
     def flip_flags(self, seed, n):
         """the flag bytes ``TensorRandomFlip`` draws under ``FixRandomSeed(seed)`` for n samples (new_epocher.py:154-155),
         on the device (a pinned host buffer and an asynchronous copy: no synchronisation)"""

@@ -17,12 +17,25 @@ soft-maxes, both arg-maxes, both directions' cross-entropy and both gradients). 
 with weight n_seg / n_total: the sum is the mean over all pixels of all listed maps.  The hook returns ``peer_sup + weight *
 cross``.
 
+CutMix (``"cutmix"`` in ``on``; off by default; French et al., BMVC 2020, the CPS paper's headline row): the strong perturbation
+of this package.  A call draws one box per unlabelled slice on the device (functional.cutmix_boxes from the seed word ``draw``),
+mixes ``unlabeled_image`` with itself rolled by one (functional.cutmix_images), runs the model and the peer on the mixed batch
+WITH gradient (``SemiSupervisedEpocher._forward_unlabeled``: under ``two_stage`` inside the epocher's ``disable_bn`` context, for
+both networks) and takes ONE launch of functional.cross_pseudo_ce_mixed: the teachers are the two networks' logits on the
+UNMIXED ``unlabeled_image`` -- the pass the step has already made --, read through the boxes; no mixed teacher map is built.
+The term enters like any other map, n_unl of the n_total slices.  ``on: [cutmix]`` alone is the official CPS + CutMix: the
+supervised losses plus the mixed term.  ``cutmix = {"prop_range": [0.25, 0.5], "seed": 0}``: the range of a box's share of the
+image area and the first seed word; ``draw`` is a registered int32 buffer, advanced by one per call and checkpointed, so a
+resumed run draws the boxes the uninterrupted one would.  A batch of fewer than two unlabelled slices has nothing to mix with:
+a RuntimeError.
+
 ``threshold``: one float or a list of C floats in [0, 1]: a network teaches a pixel only where its confidence reaches the
 threshold of the class it predicts.  The default 0 is plain CPS (no threshold vector is passed).  The thresholds are the
 buffer ``tau`` of the trainer hook.
 
 Meters, all formed on the device (no synchronisation per step): ``loss`` (the cross term), ``peer_sup_loss``, ``agree`` (the
-share of pixels on which the two arg-maxes agree) and ``kept`` (kept pixels of both directions / (2 * pixels)).
+share of pixels on which the two arg-maxes agree) and ``kept`` (kept pixels of both directions / (2 * pixels)); with CutMix on,
+``mixed`` as well (the share of the mixed batch's pixels that lie inside a box).
 
 ``val()`` and ``inference()`` use the model alone; the trained peer is in ``__hooks__`` of every checkpoint."""
 import torch
@@ -35,7 +48,9 @@ from ..epochers.helper import supervised_loss
 from .mt import compute_dtype_pairs, match_compute_dtype
 from .utils import meter_focus
 
-MAPS = ("labeled", "unlabeled", "unlabeled_tf")
+MAPS = ("labeled", "unlabeled", "unlabeled_tf", "cutmix")
+DEFAULT_ON = MAPS[:3]  # "cutmix" is never on unless it is named
+CUTMIX_DEFAULTS = {"prop_range": (0.25, 0.5), "seed": 0}
 
 
 def _build_peer(model: nn.Module, peer_seed: int) -> nn.Module:
@@ -55,8 +70,8 @@ def _same_parameters(a: nn.Module, b: nn.Module) -> bool:
 
 class CrossPseudoTrainerHook(TrainerHook):
 
-    def __init__(self, name: str, weight: float, model: nn.Module, threshold=0.0, peer_seed: int = 1, on=MAPS,
-                 peer: nn.Module = None):
+    def __init__(self, name: str, weight: float, model: nn.Module, threshold=0.0, peer_seed: int = 1, on=DEFAULT_ON,
+                 peer: nn.Module = None, cutmix=None):
         on = (on,) if isinstance(on, str) else tuple(on)
         if len(on) == 0:
             raise ValueError(f"CrossPseudoTrainerHook: `on` is empty (some of {MAPS})")
@@ -69,6 +84,25 @@ class CrossPseudoTrainerHook(TrainerHook):
         for v in (values if values is not None else [float(threshold)]):
             if not 0.0 <= v <= 1.0:
                 raise ValueError(f"CrossPseudoTrainerHook: threshold {v} outside [0, 1]")
+        prop_range, draw = None, None
+        if cutmix is not None and "cutmix" not in on:
+            raise ValueError(f"CrossPseudoTrainerHook: a `cutmix` section is given but `on` = {on} does not name \"cutmix\" -- "
+                             "add it to `on`, or drop the section")
+        if "cutmix" in on:
+            section = dict(CUTMIX_DEFAULTS, **(dict(cutmix) if cutmix is not None else {}))
+            unknown = sorted(set(section) - set(CUTMIX_DEFAULTS))
+            if unknown:
+                raise ValueError(f"CrossPseudoTrainerHook: `cutmix` has no key {unknown} (some of {sorted(CUTMIX_DEFAULTS)})")
+            try:
+                prop_range = tuple(float(v) for v in section["prop_range"])
+            except (TypeError, ValueError):
+                prop_range = ()
+            if len(prop_range) != 2 or not 0.0 < prop_range[0] <= prop_range[1] <= 1.0:
+                raise ValueError(f"CrossPseudoTrainerHook: cutmix prop_range {section['prop_range']!r} must be a pair with "
+                                 "0 < lo <= hi <= 1")
+            draw = section["seed"]
+            if isinstance(draw, bool) or not isinstance(draw, int) or not 0 <= draw < 2 ** 31:
+                raise ValueError(f"CrossPseudoTrainerHook: cutmix seed must be an integer in [0, 2^31), given {draw!r}")
         classes = int(model.num_classes)
         if values is not None and len(values) != classes:
             raise ValueError(f"CrossPseudoTrainerHook: {len(values)} thresholds for {classes} classes")
@@ -83,6 +117,19 @@ class CrossPseudoTrainerHook(TrainerHook):
         fixed = values if values is not None else [float(threshold)] * classes
         self._plain = all(v == 0.0 for v in fixed)  # plain CPS: no threshold vector is passed
         self.register_buffer("tau", torch.tensor(fixed, dtype=torch.float32))
+        self._prop_range = prop_range  # None: no CutMix, and neither the buffer nor the meter below exists
+        if prop_range is not None:
+            self.register_buffer("draw", torch.tensor([draw], dtype=torch.int32))
+
+    @property
+    def cutmix(self) -> bool:
+        return self._prop_range is not None
+
+    def seed_word(self, device):
+        """the box sampler's seed word on ``device`` (moved once when the hook itself was not)"""
+        if self.draw.device != device:
+            self.draw = self.draw.to(device)
+        return self.draw
 
     @property
     def learnable_modules(self):
@@ -114,12 +161,13 @@ class _CrossPseudoEpocherHook(EpocherHook):
 
     @meter_focus
     def configure_meters(self, meters):
-        for key in ("loss", "peer_sup_loss", "agree", "kept"):
+        for key in ("loss", "peer_sup_loss", "agree", "kept") + (("mixed",) if self._owner.cutmix else ()):
             self.meters.register_meter(key, AverageValueMeter())
 
     def graph_key(self):
         owner = self._owner
-        return (type(self).__name__, float(self._weight), owner._on, "plain" if owner._plain else "tau")
+        key = (type(self).__name__, float(self._weight), owner._on, "plain" if owner._plain else "tau")
+        return key + (owner._prop_range,) if owner.cutmix else key
 
     def before_forward_pass(self, **kwargs):
         # references, not copies: the same three batches the model is about to see
@@ -144,19 +192,29 @@ class _CrossPseudoEpocherHook(EpocherHook):
             self._dtype_pairs = compute_dtype_pairs(epocher._model, peer)
         match_compute_dtype(self._dtype_pairs)
         labeled_image, unlabeled_image, unlabeled_image_tf = images
+        if owner.cutmix and len(unlabeled_image) < 2:
+            raise RuntimeError(f"{type(owner).__name__}: CutMix mixes every unlabelled slice with the next one of its batch; "
+                               f"this batch holds {len(unlabeled_image)} unlabelled slice(s), fewer than two")
         peer_logits = epocher._forward_pass(labeled_image=labeled_image, unlabeled_image=unlabeled_image,
                                             unlabeled_image_tf=unlabeled_image_tf, model=peer)
         peer_sup, _ = supervised_loss(epocher._sup_criterion, peer_logits[0], labeled_target, epocher.num_classes)
-        student = dict(zip(MAPS, (label_logits, unlabeled_logits, unlabeled_tf_logits)))
-        theirs = dict(zip(MAPS, peer_logits))
-        n_total = sum(len(student[m]) for m in owner._on)
+        student = dict(zip(DEFAULT_ON, (label_logits, unlabeled_logits, unlabeled_tf_logits)))
+        theirs = dict(zip(DEFAULT_ON, peer_logits))
+        n_unl = len(unlabeled_image)
+        n_total = sum(n_unl if m == "cutmix" else len(student[m]) for m in owner._on)
         tau = owner.thresholds(unlabeled_tf_logits.device)
         C = unlabeled_tf_logits.shape[1]
         cross, agree, kept, pixels = None, None, None, 0
         for m in owner._on:
-            s, p = student[m], theirs[m]
             out = []
-            term = F_hip.cross_pseudo_ce(s, p, tau, len(s) / n_total, out=out)
+            if m == "cutmix":
+                s = unlabeled_logits
+                term = self._cutmix_term(unlabeled_image, unlabeled_logits, theirs["unlabeled"], tau, n_unl / n_total, out)
+                inside = out[1][4 * C + 1]
+                self.meters["mixed"].add(inside.to(torch.float32) / float(s.shape[0] * s.shape[2] * s.shape[3]))
+            else:
+                s, p = student[m], theirs[m]
+                term = F_hip.cross_pseudo_ce(s, p, tau, len(s) / n_total, out=out)
             hist = out[1]
             a, k = hist[4 * C], hist[2 * C:4 * C].sum()
             cross = term if cross is None else cross + term
@@ -168,3 +226,20 @@ class _CrossPseudoEpocherHook(EpocherHook):
         self.meters["agree"].add(agree.to(torch.float32) / float(pixels))
         self.meters["kept"].add(kept.to(torch.float32) / float(2 * pixels))
         return peer_sup + self._weight * cross
+
+    def _cutmix_term(self, unlabeled_image, unlabeled_logits, peer_unlabeled, tau, share, out):
+        """boxes from the seed word, the mixed batch, both networks on it, the criterion read through the boxes"""
+        owner, epocher = self._owner, self.epocher
+        n_unl, _, H, W = unlabeled_image.shape
+        if tuple(unlabeled_logits.shape[2:]) != (H, W) or tuple(peer_unlabeled.shape[2:]) != (H, W):
+            raise RuntimeError(f"{type(owner).__name__}: CutMix draws its boxes for the {H} x {W} images and reads the class maps "
+                               f"through the same boxes, but the networks return {tuple(unlabeled_logits.shape[2:])} / "
+                               f"{tuple(peer_unlabeled.shape[2:])} maps -- it needs a network whose output has its input's size")
+        draw = owner.seed_word(unlabeled_image.device)
+        boxes = F_hip.cutmix_boxes(draw, n_unl, H, W, owner._prop_range)
+        draw.add_(1)
+        mixed = F_hip.cutmix_images(unlabeled_image, boxes, 1)
+        model_mixed = epocher._forward_unlabeled(mixed)
+        peer_mixed = epocher._forward_unlabeled(mixed, model=owner.peer)
+        return F_hip.cross_pseudo_ce_mixed(model_mixed, peer_mixed, unlabeled_logits.detach(), peer_unlabeled.detach(), boxes, 1,
+                                           tau, share, out=out)

@@ -182,10 +182,13 @@ def create_pixel_contrast_hook(*, model, weight: float, feature_name: str = "Up_
 
 
 def create_cross_pseudo_hook(*, model, weight: float, threshold=0.0, peer_seed: int = 1,
-                             on=("labeled", "unlabeled", "unlabeled_tf")):
+                             on=("labeled", "unlabeled", "unlabeled_tf"), cutmix=None):
     """``CrossPseudoParameters``: cross pseudo supervision with a peer network of the model's class, initialised under
-    ``peer_seed`` (semi_seg/hooks/cps.py); ``threshold`` 0 is plain CPS, ``on`` names the class maps the cross term covers"""
-    return CrossPseudoTrainerHook(name="cps", weight=weight, model=model, threshold=threshold, peer_seed=peer_seed, on=on)
+    ``peer_seed`` (semi_seg/hooks/cps.py); ``threshold`` 0 is plain CPS, ``on`` names the class maps the cross term covers.
+    ``"cutmix"`` in ``on`` adds the CutMix term (``on: [cutmix]`` alone is the official CPS + CutMix); ``cutmix`` = {"prop_range":
+    [lo, hi], "seed": s} sets its box-area range and first seed word (defaults [0.25, 0.5] and 0)"""
+    return CrossPseudoTrainerHook(name="cps", weight=weight, model=model, threshold=threshold, peer_seed=peer_seed, on=on,
+                                  cutmix=cutmix)
 
 
 def create_entropy_min_hook(*, weight: float):
