@@ -36,7 +36,7 @@ extern "C" {
 /* Bumped whenever a struct layout, a limit (SPCL_*_MAX) or an entry point's meaning changes.  The library is git-ignored and
  * travels next to the sources: the Python binding (native.py) refuses a library whose version is not the header's, so that a
  * stale build fails at load time instead of running kernels on structs of another stride. */
-#define SPCL_ABI_VERSION 36
+#define SPCL_ABI_VERSION 37
 int spcl_abi_version(void);
 const char* spcl_last_error(void);
 
@@ -1601,6 +1601,67 @@ int spcl_cross_pseudo_ce_mixed(const float* s_a, const float* s_b, const float* 
                                const int32_t* boxes, int roll, const float* tau, float weight, float* loss, float* parts,
                                float* da, float* db, unsigned long long* hist, uint8_t* label_a, uint8_t* label_b, void* ws,
                                size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- strong intensity view (csrc/strong_view.hip) ----------------
+ * The strong view of the unlabelled pair (FixMatch / UniMatch; the op family is nnU-Net's intensity augmentation), ABI 37; not
+ * in the reference.  spcl_strong_view_params draws one row of 16 floats per sample; spcl_strong_view_apply is spcl_flip_batch
+ * with the row's ops applied on the way.  Nothing is read back, each entry is one capturable launch, all outputs are bitwise
+ * reproducible, no floating-point atomics.
+ *
+ *   table f32 [N][SPCL_SV_COLS = 16]:
+ *     0 gamma   1 contrast c   2 brightness b   3 blur t   4 noise sigma      (the neutral value where the op is not applied)
+ *     5 applied: sum of 2^k over the applied ops k, as a float   6 the sample's noise seed word, bit-cast
+ *     7 m: the mean of sample n   8 the number of applied ops, as a float   9 .. 15 zero
+ *
+ *   spcl_strong_view_params: x [N][C][H][W] f32 / bf16 (read for the mean only); seed: ONE 32-bit word in device memory (read
+ *                    by the kernel: a captured call replays with what the word holds then); cfg: 15 HOST words, for op k = 0
+ *                    gamma, 1 contrast, 2 brightness, 3 blur, 4 noise: cfg[3 k] = p16_k, the gate probability in units of
+ *                    1 / 65536 (0 .. 65536), cfg[3 k + 1], cfg[3 k + 2] = the bits of the f32 range ends lo_k, hi_k.  With
+ *                    key(i) = pxs_key(i, *seed) (spcl_pixel_sample's key):
+ *                      r_j = key(16 n + j), j = 0 .. 10;  u_j = r_j >> 8
+ *                      op k is applied iff (r_{2k} & 0xFFFF) < p16_k
+ *                      v_k = min(hi_k, lo_k + (hi_k - lo_k) * (float(u_{2k+1}) * 2^-24))
+ *                    in f32: the difference, the product and the sum are each rounded to nearest once (no fused
+ *                    multiply-add; the scaling by 2^-24 and the min are exact), so a float32 host restatement is bit-equal.
+ *                    (The min only bites where the rounded difference carries the sum one spacing past hi_k.)  An op that is
+ *                    not applied stores 1, 1, 1, 0, 0, bit-exact.  Column 6 = r_10.  Column 7: the C H W source elements of
+ *                    sample n summed in float64 in a fixed association (thread t of 256 adds elements t, t + 256, ... in
+ *                    order; the xor butterfly of the wave, offsets 32 .. 1; the four waves in order), divided by C H W,
+ *                    rounded to f32 once.  One workgroup per sample.
+ *                    Refused: a null pointer, a bad dtype, N outside [1, 2^20], a non-positive extent, C H W >= 2^31, p16
+ *                    outside [0, 65536], lo > hi (or a NaN), gamma or brightness lo <= 0, contrast lo < 0, blur range outside
+ *                    [0, 1], noise lo < 0.
+ *   spcl_strong_view_apply: x, out contiguous [N][C][H][W] f32 / bf16, out != x; flags uint8 [N] as spcl_flip_batch (bit 0
+ *                    flips H, bit 1 flips W).  For the output pixel p = (n, c, h, w) with the source pixel s = flip(p), in f32:
+ *                      1  a = clamp(x[s], 0, 1);  a = powf(a, gamma_n), not taken (bit-exact) where gamma_n == 1
+ *                      2  a = ((a - m_n) * c_n + m_n) * b_n
+ *                      3  a = a + t_n * (B(a) - a), B the separable binomial filter [1 4 6 4 1] / 16 (dyadic weights) along W,
+ *                         then along H, of the image after 1 - 2 with replicated edges: the coordinate is clamped before the
+ *                         load, no index is formed from a table value.  The filter is symmetric and the edges replicate, so it
+ *                         commutes with the flip: it is taken in the output frame.  Not taken where t_n == 0.
+ *                      4  q = (c H + h) W + w (the OUTPUT frame);  k_i = pxs_key(2 q + i, seed word of n), i = 0, 1;
+ *                         z = (k_0 & 0xFFFF) + (k_0 >> 16) + (k_1 & 0xFFFF) + (k_1 >> 16) - 131070  (an Irwin-Hall sum of four
+ *                         16-bit uniforms, exact in an int; variance 4 (2^32 - 1) / 12);
+ *                         a += (sigma_n * sqrt(3)_f32) * (float(z) * 2^-16): variance sigma_n^2 up to 2^-32 (the scaling of z
+ *                         is exact; the last product and the sum may be one fused multiply-add).  Not taken where
+ *                         sigma_n == 0.
+ *                      5  out[p] = clamp(a, 0, 1), stored in dtype (bf16: round to nearest even).
+ *                    A sample whose five values are all neutral is a pure copy (no clamp, no arithmetic): with every row
+ *                    neutral the call is spcl_flip_batch, bit for bit.  A workgroup owns a SPCL_SV_TILE_H x SPCL_SV_TILE_W
+ *                    tile of one (n, c) plane; with blur the tile and a halo of 2 are staged in LDS with steps 1 - 2 applied
+ *                    at the load.  Where W elements are a multiple of 16 bytes and both pointers are 16-byte aligned a thread
+ *                    loads and stores 16 bytes at a time (the halo staging of the blur reads element-wise), else element by
+ *                    element.
+ *                    Refused: a null pointer, a bad dtype, a non-positive extent, C H W >= 2^31 (and N C H W / 1024 tiles
+ *                    past 2^31), out == x. */
+#define SPCL_SV_COLS 16
+#define SPCL_SV_TILE_H 16
+#define SPCL_SV_TILE_W 64
+int spcl_strong_view_params(const void* x, int dtype, int N, int C, int H, int W, const uint32_t* seed, const int32_t* cfg,
+                            float* table, void* stream);
+int spcl_strong_view_apply(const void* x, void* out, int dtype, int N, int C, int H, int W, const uint8_t* flags,
+                           const float* table, void* stream);
+int spcl_strong_view_tile(int* tile_h, int* tile_w);
 
 #ifdef __cplusplus
 }

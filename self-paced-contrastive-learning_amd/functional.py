@@ -6,6 +6,7 @@ import collections
 import ctypes
 import math
 import os
+import struct
 from ctypes import c_double, c_float, c_int
 
 import torch
@@ -4062,6 +4063,157 @@ def cross_pseudo_ce_mixed(s_a, s_b, t_a, t_b, boxes=None, roll=1, tau=None, weig
         return loss, da, db
 
     return _PixelCriterion2Fn.apply(s_a, s_b, launch)
+
+
+# ------------------------------------------------------- strong intensity view of the unlabelled pair (csrc/strong_view.hip)
+STRONG_VIEW_OPS = ("gamma", "contrast", "brightness", "blur", "noise")
+STRONG_VIEW_NEUTRAL = (1.0, 1.0, 1.0, 0.0, 0.0)
+# nnU-Net's intensity ranges restated for [0, 1] images (their effect on Dice is not measured)
+STRONG_VIEW_DEFAULTS = {"gamma": {"p": 0.3, "range": (0.7, 1.5)}, "contrast": {"p": 0.5, "range": (0.75, 1.25)},
+                        "brightness": {"p": 0.5, "range": (0.75, 1.25)}, "blur": {"p": 0.2, "range": (0.25, 1.0)},
+                        "noise": {"p": 0.15, "range": (0.0, 0.05)}}
+STRONG_VIEW_COLS = 16  # == SPCL_SV_COLS; columns: the five values, applied mask, noise seed word, mean, applied count
+STRONG_VIEW_MAX_N = 1 << 20
+
+
+def _f32(v: float) -> float:
+    return struct.unpack("<f", struct.pack("<f", v))[0]
+
+
+class StrongViewConfig:
+    """The five intensity ops of ``strong_view``: for each of ``STRONG_VIEW_OPS`` a gate probability ``p`` in [0, 1] and a
+    value ``range`` (lo, hi); an op left out keeps its entry of ``STRONG_VIEW_DEFAULTS``.  Normalised to what the kernel reads:
+    ``p16 = round(p * 65536)`` and the range ends rounded to float32.  gamma is the exponent of the [0, 1]-clamped image,
+    contrast the factor about the sample's mean, brightness a factor, blur the share t in [0, 1] of the binomial filter
+    [1 4 6 4 1] / 16 (t = 1: variance 1), noise the standard deviation.  Every refusal is a ``ValueError`` on the host."""
+
+    def __init__(self, **ops):
+        unknown = sorted(set(ops) - set(STRONG_VIEW_OPS))
+        if unknown:
+            raise ValueError(f"StrongViewConfig: no op {unknown} (some of {list(STRONG_VIEW_OPS)})")
+        self.p16, self.lo, self.hi = [], [], []
+        for name in STRONG_VIEW_OPS:
+            given = ops.get(name)
+            if given is not None and not hasattr(given, "keys"):
+                raise ValueError(f"StrongViewConfig: {name} must be a mapping with `p` and `range`, given {given!r}")
+            section = dict(STRONG_VIEW_DEFAULTS[name], **(dict(given) if given is not None else {}))
+            extra = sorted(set(section) - {"p", "range"})
+            if extra:
+                raise ValueError(f"StrongViewConfig: {name} has no key {extra} (`p` and `range`)")
+            p = section["p"]
+            if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+                raise ValueError(f"StrongViewConfig: {name} p = {p!r} must be a number in [0, 1]")
+            try:
+                lo, hi = (_f32(float(v)) for v in section["range"])
+            except (TypeError, ValueError, OverflowError, struct.error):
+                raise ValueError(f"StrongViewConfig: {name} range must be a pair (lo, hi) of float32 numbers, given "
+                                 f"{section['range']!r}") from None
+            if not lo <= hi < float("inf"):
+                raise ValueError(f"StrongViewConfig: {name} range ({lo}, {hi}) must be finite with lo <= hi")
+            if name in ("gamma", "brightness") and not lo > 0.0:
+                raise ValueError(f"StrongViewConfig: {name} range ({lo}, {hi}) must lie above 0")
+            if name in ("contrast", "noise") and lo < 0.0:
+                raise ValueError(f"StrongViewConfig: {name} range ({lo}, {hi}) must not be negative")
+            if name == "blur" and not (0.0 <= lo and hi <= 1.0):
+                raise ValueError(f"StrongViewConfig: blur range ({lo}, {hi}) must lie in [0, 1] (the share of the binomial "
+                                 "filter: variance at most 1)")
+            self.p16.append(int(round(float(p) * 65536)))
+            self.lo.append(lo)
+            self.hi.append(hi)
+
+    @classmethod
+    def off(cls):
+        """every gate at 0: the view is the plain flip"""
+        return cls(**{name: {"p": 0.0} for name in STRONG_VIEW_OPS})
+
+    def key(self):
+        """the normalised config as a hashable value"""
+        return tuple((name, self.p16[k], self.lo[k], self.hi[k]) for k, name in enumerate(STRONG_VIEW_OPS))
+
+    def words(self):
+        """the 15 host words of ``spcl_strong_view_params``: p16, bits of lo, bits of hi for each op"""
+        w = []
+        for k in range(len(STRONG_VIEW_OPS)):
+            w += [self.p16[k]] + [struct.unpack("<i", struct.pack("<f", v))[0] for v in (self.lo[k], self.hi[k])]
+        return (ctypes.c_int32 * len(w))(*w)
+
+    def __eq__(self, other):
+        return isinstance(other, StrongViewConfig) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return "StrongViewConfig(" + ", ".join(f"{n}={{'p': {p / 65536:g}, 'range': ({lo:g}, {hi:g})}}"
+                                               for n, p, lo, hi in self.key()) + ")"
+
+
+def strong_view_tile():
+    """(T_h, T_w): the tile one workgroup of ``spcl_strong_view_apply`` owns"""
+    th, tw = ctypes.c_int(0), ctypes.c_int(0)
+    _n.call("spcl_strong_view_tile", ctypes.byref(th), ctypes.byref(tw))
+    return th.value, tw.value
+
+
+def _strong_view_image(x, what):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16) or x.numel() == 0:
+        raise ValueError(f"{what} takes a non-empty float32 or bfloat16 [N, C, H, W] batch, given "
+                         f"{getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}")
+    if x.requires_grad:
+        raise ValueError(f"{what}: the batch requires a gradient -- the strong view has no backward (images carry none)")
+    _n.require_gpu(x)
+    if x.shape[0] > STRONG_VIEW_MAX_N:
+        raise ValueError(f"{what}: N = {x.shape[0]} samples (at most {STRONG_VIEW_MAX_N})")
+    if x[0].numel() >= 2 ** 31:
+        raise ValueError(f"{what}: a sample of {tuple(x.shape[1:])} has 2^31 elements or more")
+    return x.contiguous()
+
+
+def strong_view_params(x, seed, cfg):
+    """The per-sample table of the strong view (``spcl_strong_view_params``, one launch, one workgroup per sample) -> f32
+    [N, 16]: columns 0 - 4 the values of gamma, contrast, brightness, blur, noise (the neutral 1, 1, 1, 0, 0 where the op's gate
+    stayed shut), 5 the mask of applied ops as a float, 6 the sample's noise seed word bit-cast, 7 the mean of the sample
+    (float64 sum in a fixed order, rounded once), 8 the number of applied ops.  ``seed``: a Python int in [0, 2^32) or a
+    one-element int32 device tensor (read by the kernel: a captured call replays with what it holds then).  ``cfg``: a
+    ``StrongViewConfig``.  include/spcl_hip.h states the rule; tests/_strong_view_oracle.py restates it bit for bit."""
+    if not isinstance(cfg, StrongViewConfig):
+        raise ValueError(f"strong_view_params: cfg must be a StrongViewConfig, given {type(cfg).__name__}")
+    _pixel_seed_check(seed)
+    xc = _strong_view_image(x, "strong_view_params")
+    N, C, H, W = xc.shape
+    sd = _pixel_seed_arg(seed, xc.device)
+    table = torch.empty((N, STRONG_VIEW_COLS), dtype=torch.float32, device=xc.device)
+    _n.call("spcl_strong_view_params", _n.ptr(xc), _n.dtype_code(xc.dtype), N, C, H, W, _n.ptr(sd), cfg.words(),
+            _n.ptr(table), _n.stream())
+    return table
+
+
+def strong_view_apply(x, flags, table):
+    """``flip_batch(x, flags)`` with the table's ops applied on the way (``spcl_strong_view_apply``, one launch): clamp to
+    [0, 1] and gamma, contrast about the mean and brightness, the binomial blur, the integer Irwin-Hall noise, clamp.  A sample
+    whose row is all-neutral is a pure copy: with every row neutral the result is ``flip_batch``'s, bit for bit.  ``flags``:
+    uint8 [N] on the device (bit 0 flips H, bit 1 flips W); ``table``: f32 [N, 16] (``strong_view_params``).  No autograd."""
+    xc = _strong_view_image(x, "strong_view_apply")
+    N, C, H, W = xc.shape
+    if not isinstance(flags, torch.Tensor) or flags.dtype != torch.uint8 or tuple(flags.shape) != (N,) or \
+            flags.device != xc.device:
+        raise ValueError(f"strong_view_apply: `flags` must be a torch.uint8 [{N}] tensor on {xc.device}")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or \
+            tuple(table.shape) != (N, STRONG_VIEW_COLS) or table.device != xc.device:
+        raise ValueError(f"strong_view_apply: `table` must be a torch.float32 [{N}, {STRONG_VIEW_COLS}] tensor on {xc.device}")
+    out = torch.empty_like(xc)
+    _n.call("spcl_strong_view_apply", _n.ptr(xc), _n.ptr(out), _n.dtype_code(xc.dtype), N, C, H, W,
+            _n.ptr(flags.contiguous()), _n.ptr(table.detach().contiguous()), _n.stream())
+    return out
+
+
+def strong_view(x, flags, seed, cfg, out=None):
+    """``strong_view_apply(x, flags, strong_view_params(x, seed, cfg))``: two launches.  ``out``: a list that receives the
+    table."""
+    table = strong_view_params(x, seed, cfg)
+    if out is not None:
+        out.append(table)
+    return strong_view_apply(x, flags, table)
 
 
 # --------------------------------------------------------------------- label-guided pixel contrast (csrc/pixel_contrast.hip)

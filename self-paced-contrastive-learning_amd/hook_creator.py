@@ -39,7 +39,11 @@ Refused during pre-training (it needs the labelled batch's label maps).
 ``CrossPseudoParameters`` builds cross pseudo supervision (``create_cross_pseudo_hook``, hook name ``cps``: a peer network of
 the model's class, each trained towards the other's arg-max prediction): ``weight``, ``threshold``, ``peer_seed``, ``on`` and
 ``cutmix`` (``{prop_range, seed}``; with ``"cutmix"`` in ``on`` the hook adds the CutMix term on a box-mixed unlabelled batch).
-Not in the reference.  Refused during pre-training (the peer's own objective is the supervised loss)."""
+Not in the reference.  Refused during pre-training (the peer's own objective is the supervised loss).
+``StrongViewParameters`` builds the strong intensity view of the unlabelled pair (``create_strong_view_hook``, hook name
+``strongview``: the second view is the flip with gamma, contrast, brightness, blur and noise applied on the way): ``seed`` and
+one section ``{p, range}`` per op.  It adds no loss; every hook that reads ``unlabeled_tf_logits`` trains on it.  Not in the
+reference.  Refused during pre-training (the pre-train epocher has its own augmentation recipe)."""
 from .semi_seg import hooks as _hooks
 
 # config section -> (factory in semi_seg.hooks, does the factory take max_epoch?)
@@ -60,6 +64,7 @@ _SEMI_SECTIONS = (
     ("PseudoLabelParameters", "create_pseudo_label_hook", True, False),
     ("PixelContrastParameters", "create_pixel_contrast_hook", True, False),
     ("CrossPseudoParameters", "create_cross_pseudo_hook", True, False),
+    ("StrongViewParameters", "create_strong_view_hook", False, False),
 )
 
 

@@ -295,6 +295,10 @@ _SIGNATURES = {
     "spcl_cross_pseudo_mixed_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "spcl_cross_pseudo_ce_mixed": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_float, _P, _P, _P, _P, _P,
                                            _P, _P, _P, c_size_t, _P]),
+    # strong intensity view of the unlabelled pair: per-sample table, flip + ops in one launch (csrc/strong_view.hip)
+    "spcl_strong_view_params": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "spcl_strong_view_apply": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "spcl_strong_view_tile": (c_int, [_P, _P]),
     # mix-up (csrc/semi_reg.hip)
     "spcl_mixup_images": (c_int, [_P, _P, _P, c_int, c_size_t, c_float, c_float, _P, _P]),
     "spcl_mixup_kl_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
@@ -375,7 +379,7 @@ class WgradTail(ctypes.Structure):
                 ("nblk_co", c_int), ("CIB", c_int), ("COB", c_int), ("Cin", c_int), ("Cout", c_int)]
 
 
-ABI_VERSION = 36  # == SPCL_ABI_VERSION of include/spcl_hip.h (tests/test_abi.py compares them); lib() refuses any other library
+ABI_VERSION = 37  # == SPCL_ABI_VERSION of include/spcl_hip.h (tests/test_abi.py compares them); lib() refuses any other library
 WGRAD_BATCH_MAX = 16
 WGRAD_TAILS_MAX = 16
 _NO_STATUS = ("spcl_abi_version", "spcl_block1_recompute_supported", "spcl_block1_kernels_take", "spcl_conv16_bwd_fused_image_supported", "spcl_conv3x3_forward_image_acorr_rows", "spcl_image_autocorr_rows", "spcl_conv_dgrad_bnstats_image_supported", "spcl_conv16_bwd_fused_supported", "spcl_conv16_bwd_fused_splits", "spcl_conv_num_tiles", "spcl_conv_stat_rows", "spcl_conv_set_gemm", "spcl_conv_set_f32_split", "spcl_conv_get_f32_split", "spcl_supcon_unit_gradient_block", "spcl_conv_cat_supported", "spcl_conv_up2_supported", "spcl_conv_split_supported", "spcl_conv_split_bnstats_supported", "spcl_conv1x1_bwd_rows", "spcl_profile_count", "spcl_conv_dgrad_bnstats_supported", "spcl_conv_dgrad_poolstats_supported",

@@ -6,7 +6,9 @@ regularisation keyword set (:176-187), so the InfoNCE hooks run under it as well
 added for the HIP hooks: ``unlabeled_logits`` (before the flip) and ``flip_flags`` (uint8 [n] on the device: bit 0 flips H,
 bit 1 flips W -- what ``TensorRandomFlip`` draws under ``FixRandomSeed(seed)``), so the flipped copies are read by
 indexing; and two for the hooks that use the labelled batch (semi_seg/hooks/pixelcontrast.py): ``labeled_target`` (the label
-maps [n_l, H, W]) and ``label_logits``.  The flipped second view is one ``spcl_flip_batch`` launch; the supervised loss and Dice counts are the fused
+maps [n_l, H, W]) and ``label_logits``.  The flipped second view is one ``spcl_flip_batch`` launch -- or, when one hook offers
+``strong_view(image_cf, flags)`` (semi_seg/hooks/strongview.py), that hook's strong intensity view of the same flip; the
+supervised loss and Dice counts are the fused
 launch of ``FineTuneEpocher``; model and hook parameters are one ``FlatParams`` stepped by ``FusedRAdam``, whose
 coefficient launch carries the meters' device adds.  No host synchronisation per step; eager launches (no hipGraph)."""
 import random
@@ -24,8 +26,19 @@ from .finetune import _EpocherBase, unzip_twice_transformed_labeled
 from .helper import FixRandomSeed, TensorRandomFlip, begin_epoch, supervised_loss
 
 
+def _offers_strong_view(hook):
+    return callable(getattr(hook, "strong_view", None))
+
+
+def _nested_strong_view(hook):
+    """does a member of a ``CombineEpochHook`` (at any depth) offer ``strong_view``?"""
+    members = getattr(hook, "_epocher_hook", ())
+    return any(_offers_strong_view(m) or _nested_strong_view(m) for m in members)
+
+
 class SemiSupervisedEpocher(_EpocherBase):
     meter_focus = "semi"
+    _strong_view = None  # the one hook that offers ``strong_view`` (set by ``add_hook``), or None: the plain flip
 
     def __init__(self, *, model: nn.Module, optimizer, labeled_loader: Iterable, unlabeled_loader: Iterable, sup_criterion,
                  num_batches: int, cur_epoch=0, device="cuda", two_stage: bool = False, disable_bn: bool = False,
@@ -54,6 +67,14 @@ class SemiSupervisedEpocher(_EpocherBase):
 
     # ---- contrastyou/epochers/base.py:47-60
     def add_hook(self, hook):
+        if _nested_strong_view(hook):
+            raise ValueError(f"{type(self).__name__}: a hook that offers `strong_view` sits inside a combined hook -- it adds no "
+                             "loss, which a CombineEpochHook cannot sum; register it with the epocher directly")
+        if _offers_strong_view(hook):
+            if self._strong_view is not None:
+                raise ValueError(f"{type(self).__name__}: a second hook offers `strong_view` -- the unlabelled pair has one "
+                                 "second view, made by one hook (drop one of the two StrongViewParameters hooks)")
+            self._strong_view = hook
         self._hooks.append(hook)
         hook.set_epocher(self)
 
@@ -98,6 +119,10 @@ class SemiSupervisedEpocher(_EpocherBase):
     def _regularization(self, **kwargs):  # new_epocher.py:234-238
         if len(self._hooks) > 0:
             losses = [h(**kwargs) for h in self._hooks]
+            # a hook marked ``contributes_loss = False`` (semi_seg/hooks/strongview.py) is called and adds nothing
+            losses = [v for h, v in zip(self._hooks, losses) if getattr(h, "contributes_loss", True)]
+            if not losses:
+                return torch.zeros((), dtype=torch.float, device=self._device)
             total = losses[0]
             for extra in losses[1:]:
                 total = total + extra
@@ -150,7 +175,10 @@ class SemiSupervisedEpocher(_EpocherBase):
         (unlabeled_image, unlabeled_image_cf), _, unlabeled_filename, unl_partition, unl_group = \
             unzip_twice_transformed_labeled(unlabeled_data, self._device)
         flags = self.flip_flags(seed, len(unlabeled_image))
-        unlabeled_image_tf = F_hip.flip_batch(unlabeled_image_cf.contiguous(), flags)
+        if self._strong_view is None:
+            unlabeled_image_tf = F_hip.flip_batch(unlabeled_image_cf.contiguous(), flags)
+        else:  # the flip with the hook's intensity ops on the way
+            unlabeled_image_tf = self._strong_view.strong_view(unlabeled_image_cf, flags)
         label_logits, unlabeled_logits, unlabeled_tf_logits = self.forward_pass(
             labeled_image=labeled_image, unlabeled_image=unlabeled_image, unlabeled_image_tf=unlabeled_image_tf)
         unlabeled_logits_tf = F_hip.flip_batch(unlabeled_logits, flags)

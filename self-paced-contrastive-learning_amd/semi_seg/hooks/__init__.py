@@ -3,7 +3,8 @@ from .creator import create_infonce_hooks, create_sp_infonce_hooks, feature_unti
 from .creator import (create_consistency_hook, create_cross_pseudo_hook, create_discrete_mi_consistency_hook,  # noqa: F401
                       create_discrete_mi_hooks, create_entropy_min_hook, create_mean_teacher_hook,
                       create_iic_estimator_hooks, create_midl_hook, create_mine_hooks, create_pica_consistency_hook, create_pica_hooks,
-                      create_pixel_contrast_hook, create_pseudo_label_hook, create_uc_mean_teacher_hook)
+                      create_pixel_contrast_hook, create_pseudo_label_hook, create_strong_view_hook,
+                      create_uc_mean_teacher_hook)
 from .consistency import ConsistencyTrainerHook  # noqa: F401
 from .cps import CrossPseudoTrainerHook  # noqa: F401
 from .discretemi import DiscreteMITrainHook  # noqa: F401
@@ -16,4 +17,5 @@ from .pica import PICATrainHook  # noqa: F401
 from .pixelcontrast import PixelContrastTrainerHook  # noqa: F401
 from .pseudolabel import PseudoLabelTrainerHook  # noqa: F401
 from .mixup import MixUpHook  # noqa: F401
+from .strongview import StrongViewTrainerHook  # noqa: F401
 from .ucmt import UCMeanTeacherTrainerHook  # noqa: F401

@@ -11,8 +11,8 @@ trainer-registry keys (semi_seg/trainers/__init__.py:11-12).  ``create_uc_mean_t
 (contrastyou/losses/pica_loss.py; the reference pairs them with the cluster heads in ``PICALossWrapper``,
 semi_seg/utils.py:242-263, and has no factory of its own for them).  ``create_pseudo_label_hook`` builds the pseudo-labelling
 baseline (FixMatch / FreeMatch thresholds) and ``create_pixel_contrast_hook`` the label-guided pixel contrast on a decoder
-feature; ``create_cross_pseudo_hook`` builds cross pseudo supervision with a peer network; the reference lacks all three
-altogether."""
+feature; ``create_cross_pseudo_hook`` builds cross pseudo supervision with a peer network; ``create_strong_view_hook`` makes the
+unlabelled pair's second view a strong intensity view; the reference lacks all four altogether."""
 from typing import List, Union
 
 from ...contrastyou.hooks.base import CombineTrainerHook
@@ -29,6 +29,7 @@ from .mt import MeanTeacherTrainerHook
 from .pica import PICATrainHook
 from .pixelcontrast import PixelContrastTrainerHook
 from .pseudolabel import PseudoLabelTrainerHook
+from .strongview import StrongViewTrainerHook
 from .ucmt import UCMeanTeacherTrainerHook
 
 
@@ -189,6 +190,13 @@ def create_cross_pseudo_hook(*, model, weight: float, threshold=0.0, peer_seed: 
     [lo, hi], "seed": s} sets its box-area range and first seed word (defaults [0.25, 0.5] and 0)"""
     return CrossPseudoTrainerHook(name="cps", weight=weight, model=model, threshold=threshold, peer_seed=peer_seed, on=on,
                                   cutmix=cutmix)
+
+
+def create_strong_view_hook(*, seed: int = 0, **ops):
+    """``StrongViewParameters``: the unlabelled pair's second view becomes a strong intensity view (semi_seg/hooks/strongview.py).
+    ``seed`` is the first seed word; ``gamma``, ``contrast``, ``brightness``, ``blur`` and ``noise`` are sections ``{p, range:
+    [lo, hi]}`` (defaults: functional.STRONG_VIEW_DEFAULTS); any other key is refused by name.  The hook adds no loss."""
+    return StrongViewTrainerHook(name="strongview", seed=seed, **ops)
 
 
 def create_entropy_min_hook(*, weight: float):
